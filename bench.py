@@ -10,7 +10,18 @@ reported.  ``value`` = world_size * K / max_rank_seconds (whole-job aggregate, w
 
 Usage::
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config auroc|map|image|bert|plumbing]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                    [--config auroc|map|image|bert|plumbing]
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, the K timed steps (+ the one
+``compute()``), the optional output dump, one JSON result line.  ``--full`` is where every side measurement lives
+(baselines, other precisions / sizes, reference comparisons); the headline run has none that takes a run of its own --
+its update/compute split is read from two events inside the timed window -- so ``--full`` changes nothing today.
+
+``--dump-outputs DIR`` (headline config) writes, after the timed window, what the caller of the timed path received from
+its ``compute()``: ``DIR/auroc.npy`` (float32 scalar) and ``DIR/confmat.npy`` (the [C, C] counts as float64, exact
+below 2^53; 8 MB at C = 1000).  The inputs come from a generator seeded per rank, so the same arguments give the same
+arrays from run to run and two builds can be compared output for output.  Rank 0 writes (``compute()`` is synced).
 
 * ``--gpus 1`` (default): one process.
 * ``--gpus N`` without ``WORLD_SIZE`` in the environment: this process launches ``torch.distributed.run`` with N
@@ -78,7 +89,8 @@ _REF_MEASURED_UPDATES_PER_SEC = 54.227  # profiles/reference_baseline_mi355x.jso
 def _parse(argv: list) -> argparse.Namespace:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 50; 2000 for --config plumbing, whose CPU steps are microseconds)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="auroc", choices=["auroc", "map", "image", "bert", "plumbing"])
     ap.add_argument("--num-classes", type=int, default=1000)
@@ -89,7 +101,37 @@ def _parse(argv: list) -> argparse.Namespace:
                     help="all-reduce the full histogram and compute every class on every rank (A/B against the default"
                          " class-sharded compute: reduce-scatter by class + all-gather of per-class AUROC)")
     ap.add_argument("--small", action="store_true", help="(secondary configs) reduced shapes for CPU smoke runs")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="(headline config) write the last compute()'s results as DIR/<name>.npy after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements that a plain run leaves out (the headline config has none)")
+    args = ap.parse_args(argv)
+    if args.steps is None:
+        args.steps = 2000 if args.config == "plumbing" else 50
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.config != "auroc":
+        ap.error("--dump-outputs is implemented for the headline config (--config auroc) only")
+    return args
+
+
+def _dump_outputs(out_dir: str, res: dict) -> None:
+    """``DIR/<name>.npy`` for every array of the timed path's ``compute()`` result (float32 / float64 only)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = (64 << 20) // max(1, len(res))  # bytes per array: 64 MB in all
+    for name, val in res.items():
+        t = val.detach().cpu()
+        # integer counts as float64 (exact below 2^53); half / bf16 as float32
+        t = t.to(torch.float64) if not t.is_floating_point() or t.dtype == torch.float64 else t.to(torch.float32)
+        arr = t.numpy()
+        if arr.nbytes > budget:
+            # a fixed, seeded sample of the flattened array (same positions in every run and every build)
+            idx = np.sort(np.random.default_rng(0).integers(0, arr.size, budget // arr.itemsize))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def _worker(args: argparse.Namespace) -> None:
@@ -193,6 +235,9 @@ def _worker(args: argparse.Namespace) -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, upd_ms = float(t[0]), float(t[1])
 
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, res)
+
     if rank == 0:
         value = world * args.steps / elapsed
         base = _baseline()
@@ -236,10 +281,9 @@ def _plumbing(args: argparse.Namespace) -> None:
 
     import plumbing_bench
 
-    steps = args.steps if args.steps != 50 else 2000  # the default K of the GPU configs is too short a CPU window
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        plumbing_bench.main(["--impl", "tmx", "--mode", "both", "--steps", str(steps), "--warmup", str(max(args.warmup, 50)), "--world", "2"])
+        plumbing_bench.main(["--impl", "tmx", "--mode", "both", "--steps", str(args.steps), "--warmup", str(max(args.warmup, 50)), "--world", "2"])
     for line in buf.getvalue().splitlines():
         r = json.loads(line)
         out = {

@@ -155,7 +155,9 @@ class RefFn:
     def __call__(self, p: Any, t: Any) -> Any:
         import sys
 
-        for path in ("/root/repo/tests/_oracle", "/root/reference/src"):
+        from tests.conftest import ORACLE_STUBS, REFERENCE_SRC
+
+        for path in (ORACLE_STUBS, REFERENCE_SRC):
             if path not in sys.path:
                 sys.path.append(path)
         import importlib

@@ -9,10 +9,10 @@ import torch
 
 from torchmetrics_forked_amd.functional.image.lpips import _LPIPS
 
-REF = "/root/reference/src/torchmetrics/functional/image/lpips_models"
+# the reference's three head files (5 to 7 [1, C, 1, 1] weight tensors each), stored as test vectors
+REF = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "golden", "lpips_models")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference lpips_models not available")
 @pytest.mark.parametrize("net", ["alex", "vgg", "squeeze"])
 def test_default_heads_equal_reference_pth(net):
     ref = torch.load(os.path.join(REF, f"{net}.pth"), map_location="cpu", weights_only=True)

@@ -28,10 +28,11 @@ import torch
 from torch import Tensor, nn
 
 import torchmetrics_forked_amd as tm
+from tests.conftest import ORACLE_STUBS, REFERENCE_SRC
 from tests.helpers.ddp import run_ddp
 from tests.helpers.testers import assert_allclose
 
-REF_PATHS = ("/root/repo/tests/_oracle", "/root/reference/src")
+REF_PATHS = (ORACLE_STUBS, REFERENCE_SRC)
 NB = 4  # batches; rank r of 2 takes batches r, r + 2
 
 
