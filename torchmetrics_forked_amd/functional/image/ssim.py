@@ -1,10 +1,16 @@
 """SSIM and multi-scale SSIM (API parity: reference ``functional/image/ssim.py:27-527``).
 
-GPU path (4-D inputs, square window, no full-image output, no autograd): ``tmx::ssim_sums`` — a fused separable
+GPU path (4-D inputs, square window, no full-image output): ``tmx::ssim_sums`` — a fused separable
 window kernel that only visits the valid windows the reference keeps after cropping its reflect-padded conv
 output, and returns per-plane sums of SSIM and contrast sensitivity (no 5·B stacked batch, no SSIM map in HBM).
+Under autograd (``preds`` or ``target`` requires grad) the same forward runs behind ``ops/image.py``'s autograd
+Function and the gradients come from ``tmx::ssim_sums_backward`` (``csrc/ssim_grad.hip``), for a fixed ``data_range``
+(float or tuple; the tuple's clamp stays a torch op in front) and fp32 / bf16 / fp16 inputs; SSIM, its contrast
+sensitivity and every MS-SSIM scale go through it.  ``data_range=None`` (c1 and c2 then depend on the inputs), fp64,
+``TMX_SSIM_NATIVE_GRAD=0`` and a second derivative (``create_graph=True``) differentiate the composition.
 Everything else follows the reference's grouped-conv formulation in PyTorch.
 """
+import os
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -19,6 +25,7 @@ from torchmetrics_forked_amd.functional.image.helper import (
     _gaussian_kernel_3d,
     _reflection_pad_3d,
 )
+from torchmetrics_forked_amd.ops.image import ssim_sums as _ssim_sums_autograd
 from torchmetrics_forked_amd.utilities.checks import _check_same_shape
 from torchmetrics_forked_amd.utilities.distributed import reduce
 
@@ -49,11 +56,18 @@ def _data_range_and_clamp(
     return preds, target, data_range
 
 
-def _native_ssim_ok(preds: Tensor, window: Sequence[int], return_full_image: bool) -> bool:
+def _needs_grad(preds: Tensor, target: Tensor) -> bool:
+    return torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad)
+
+
+def _native_ssim_ok(preds: Tensor, target: Tensor, window: Sequence[int], return_full_image: bool, input_range: bool = False) -> bool:
+    """``input_range``: ``data_range=None`` — c1 and c2 are then functions of the inputs and carry gradient."""
     if not preds.is_cuda or preds.ndim != 4 or return_full_image:
         return False
-    if torch.is_grad_enabled() and preds.requires_grad:
-        return False
+    if _needs_grad(preds, target):
+        # the native backward (csrc/ssim_grad.hip) takes constant c1 / c2 and the 32- and 16-bit float types
+        if input_range or preds.dtype == torch.float64 or os.environ.get("TMX_SSIM_NATIVE_GRAD", "1") == "0":
+            return False
     if window[0] != window[1] or window[0] not in _NATIVE_WINDOWS:
         return False
     h, w = preds.shape[-2:]
@@ -103,6 +117,7 @@ def _ssim_update(
     if any(y <= 0 for y in sigma):
         raise ValueError(f"Expected `sigma` to have positive number. Got {sigma}.")
 
+    input_range = data_range is None
     preds, target, data_range = _data_range_and_clamp(preds, target, data_range)
     c1 = (k1 * data_range) ** 2
     c2 = (k2 * data_range) ** 2
@@ -110,7 +125,8 @@ def _ssim_update(
     gks = [int(3.5 * s + 0.5) * 2 + 1 for s in sigma]
     window = gks if gaussian_kernel else list(kernel_size)
 
-    if not is_3d and _native_ssim_ok(preds, window, return_full_image) and (gaussian_kernel is False or sigma[0] == sigma[1]):
+    if (not is_3d and _native_ssim_ok(preds, target, window, return_full_image, input_range)
+            and (gaussian_kernel is False or sigma[0] == sigma[1])):
         if gaussian_kernel:
             w1 = _gaussian(gks[0], sigma[0], torch.float32, device).reshape(-1)
         else:
@@ -120,7 +136,11 @@ def _ssim_update(
         consts = torch.stack([c.to(device, torch.float32) if isinstance(c, torch.Tensor) else torch.full((), float(c), device=device)
                               for c in (c1, c2, data_range)])
         b, c, h, w = preds.shape
-        sums = torch.ops.tmx.ssim_sums(preds.reshape(b * c, h, w), target.reshape(b * c, h, w), w1, w1, consts, sse_out is not None)
+        if _needs_grad(preds, target):
+            # same forward op behind an autograd Function; its backward is the native tmx::ssim_sums_backward
+            sums = _ssim_sums_autograd(preds.reshape(b * c, h, w), target.reshape(b * c, h, w), w1, consts, sse_out is not None)
+        else:
+            sums = torch.ops.tmx.ssim_sums(preds.reshape(b * c, h, w), target.reshape(b * c, h, w), w1, w1, consts, sse_out is not None)
         if sse_out is not None:
             sse_out.append(sums[2].sum())
         n_valid = c * (h - window[0] + 1) * (w - window[1] + 1)

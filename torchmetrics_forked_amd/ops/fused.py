@@ -183,7 +183,9 @@ class _ImagePairPlan:
         target = kwargs.get("target", args[1] if len(args) > 1 else None)
         if not isinstance(preds, Tensor) or not isinstance(target, Tensor) or preds.ndim != 4 or preds.dtype != torch.float32:
             return []
-        if preds.shape != target.shape or not ops.use_native(preds) or torch.is_grad_enabled() and preds.requires_grad:
+        if preds.shape != target.shape or not ops.use_native(preds):
+            return []
+        if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):  # members update on their own, under no_grad
             return []
         if any(p.sum_squared_error.device != preds.device for p in psnrs):
             return []

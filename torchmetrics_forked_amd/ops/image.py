@@ -1,0 +1,64 @@
+"""Autograd wrapper of the fused SSIM window kernel: ``tmx::ssim_sums`` forward, ``tmx::ssim_sums_backward`` backward.
+
+The forward is the unchanged native op (value, and the fused-PSNR squared-error row where requested, are exactly what
+a call without grad returns).  The backward runs the two gfx950 kernels of ``csrc/ssim_grad.hip``.  A second
+derivative is not native: when grad mode is on inside ``backward`` (``create_graph=True``) the first-order gradients
+are recomputed through the differentiable grouped-conv composition, so double backward keeps working.
+"""
+from typing import Optional, Tuple
+
+import torch
+import torch.nn.functional as F
+from torch import Tensor
+
+
+def _composition_sums(p: Tensor, t: Tensor, w: Tensor, consts: Tensor) -> Tuple[Tensor, Tensor]:
+    """Per-plane sums of SSIM and contrast sensitivity over the valid windows, as differentiable torch ops.
+
+    ``p`` / ``t`` ``[P, H, W]``, ``w`` the 1-D window (``wy == wx``), ``consts`` ``(c1, c2, ...)`` on the device.  The valid
+    (unpadded) convolution visits exactly the windows the reference keeps after cropping its reflect-padded output."""
+    dtype = p.dtype if p.dtype in (torch.float32, torch.float64) else torch.float32
+    p, t = p.to(dtype).unsqueeze(1), t.to(dtype).unsqueeze(1)
+    w = w.to(dtype)
+    c1, c2 = consts[0].to(dtype), consts[1].to(dtype)
+    kernel = torch.outer(w, w)[None, None]
+    out = F.conv2d(torch.cat((p, t, p * p, t * t, p * t)), kernel)
+    mu_p, mu_t, e_pp, e_tt, e_pt = out.split(p.shape[0])
+    mu_pp, mu_tt, mu_pt = mu_p.pow(2), mu_t.pow(2), mu_p * mu_t
+    upper = 2 * (e_pt - mu_pt) + c2
+    lower = (e_pp - mu_pp) + (e_tt - mu_tt) + c2
+    sim = ((2 * mu_pt + c1) * upper) / ((mu_pp + mu_tt + c1) * lower)
+    return sim.double().sum((1, 2, 3)), (upper / lower).double().sum((1, 2, 3))
+
+
+class SsimSums(torch.autograd.Function):
+    """``SsimSums.apply(preds[P,H,W], target[P,H,W], w[KS], consts, with_sse) -> fp64 [2 | 3, P]`` (``tmx::ssim_sums``)."""
+
+    @staticmethod
+    def forward(ctx, preds: Tensor, target: Tensor, w: Tensor, consts: Tensor, with_sse: bool) -> Tensor:  # noqa: D102
+        ctx.save_for_backward(preds, target, w, consts)
+        return torch.ops.tmx.ssim_sums(preds, target, w, w, consts, with_sse)
+
+    @staticmethod
+    def backward(ctx, grad_sums: Tensor) -> Tuple[Optional[Tensor], ...]:  # noqa: D102
+        preds, target, w, consts = ctx.saved_tensors
+        need_p, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_p or need_t):
+            return None, None, None, None, None
+        # (a squared-error row, if any, is a by-product for the fused PSNR: it carries no gradient)
+        g_sim, g_cs = grad_sums[0], grad_sums[1]
+        if torch.is_grad_enabled():  # create_graph=True: first-order gradients with a graph, through the composition
+            with torch.enable_grad():
+                sim, cs = _composition_sums(preds, target, w, consts)
+                wrt = [x for x, need in ((preds, need_p), (target, need_t)) if need]
+                grads = list(torch.autograd.grad([sim, cs], wrt, [g_sim.to(sim.dtype), g_cs.to(cs.dtype)], create_graph=True))
+            gp = grads.pop(0) if need_p else None
+            gt = grads.pop(0) if need_t else None
+            return gp, gt, None, None, None
+        gp, gt = torch.ops.tmx.ssim_sums_backward(preds, target, w, w, consts, g_sim, g_cs, need_p, need_t)
+        return (gp if need_p else None), (gt if need_t else None), None, None, None
+
+
+def ssim_sums(preds: Tensor, target: Tensor, w: Tensor, consts: Tensor, with_sse: bool = False) -> Tensor:
+    """Differentiable per-plane SSIM / contrast-sensitivity sums of the native kernel."""
+    return SsimSums.apply(preds, target, w, consts, with_sse)
