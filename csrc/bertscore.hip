@@ -5,7 +5,8 @@
 // The reference materialises the whole [B, Lp, Lr] similarity tensor (and moves embeddings to the CPU).  Here a
 // 256-thread block computes one 64 × 64 tile of S_b with MFMA (4 waves × 2 × 2 tiles of 16 × 16), never writes it,
 // and folds it straight into the row / column maxima with 16-lane shuffles + one order-preserving integer
-// atomicMax per row / column and tile.
+// atomicMax per row / column and tile.  The maxima follow torch.max: they start from -inf, zero padding of the ragged
+// tiles never takes part, and a NaN similarity makes its row and column maximum NaN.
 //   * bf16 / fp16 embeddings: v_mfma_f32_16x16x32_{bf16,f16} (K = 32 per instruction, fp32 accumulation);
 //   * fp32 embeddings:        v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation).
 // A and B fragments are both "8 (or 1) consecutive k of one row", i.e. 16-byte loads straight from the row-major
@@ -29,6 +30,17 @@ __device__ __forceinline__ int ordered_bits(float f) {
 }
 
 __device__ __forceinline__ float from_ordered(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
+
+// IEEE 754-2019 maximum: NaN if either operand is NaN (fmaxf would drop it), torch.max semantics for the epilogues.
+// One v_maximum3_f32 per two folded values on gfx950, so the epilogues cost no more than with v_max_f32.
+__device__ __forceinline__ float bs_max(float v, float x) { return __builtin_elementwise_maximum(v, x); }
+
+// one row / column maximum of a tile into the ordered-integer table.  A NaN goes in as 0x7fffffff: a quiet-NaN pattern
+// that is the largest ordered key, so it wins every atomicMax and decodes unchanged; -inf is already the fill value.
+__device__ __forceinline__ void bs_commit(int* dst, float v) {
+  if (v != v) atomicMax(dst, 0x7fffffff);
+  else if (v > -INFINITY) atomicMax(dst, ordered_bits(v));
+}
 
 template <typename T>
 __device__ __forceinline__ bs_frag8 load8(const T* base, int64_t row, int64_t rows, int64_t D, int64_t k) {
@@ -76,12 +88,12 @@ __device__ __forceinline__ void fold_maxima(const bs_acc4 (&acc)[2][2], int64_t 
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         const int64_t col = col0 + 16 * ni + (lane & 15);
-        if (col < Lr) v = fmaxf(v, acc[mi][ni][r]);
+        if (col < Lr) v = bs_max(v, acc[mi][ni][r]);
       }
 #pragma unroll
-      for (int off = 8; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
+      for (int off = 8; off > 0; off >>= 1) v = bs_max(v, __shfl_xor(v, off, kWave));
       const int64_t row = row0 + 16 * mi + (lane >> 4) * 4 + r;
-      if ((lane & 15) == 0 && row < Lp && v > -INFINITY) atomicMax(rowmax + row, ordered_bits(v));
+      if ((lane & 15) == 0 && row < Lp) bs_commit(rowmax + row, v);
     }
   }
   // column maxima: over the 4 registers, the 4 lane groups and both row fragments
@@ -93,12 +105,12 @@ __device__ __forceinline__ void fold_maxima(const bs_acc4 (&acc)[2][2], int64_t 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t row = row0 + 16 * mi + (lane >> 4) * 4 + r;
-        if (row < Lp) v = fmaxf(v, acc[mi][ni][r]);
+        if (row < Lp) v = bs_max(v, acc[mi][ni][r]);
       }
-    v = fmaxf(v, __shfl_xor(v, 16, kWave));
-    v = fmaxf(v, __shfl_xor(v, 32, kWave));
+    v = bs_max(v, __shfl_xor(v, 16, kWave));
+    v = bs_max(v, __shfl_xor(v, 32, kWave));
     const int64_t col = col0 + 16 * ni + (lane & 15);
-    if (lane < 16 && col < Lr && v > -INFINITY) atomicMax(colmax + col, ordered_bits(v));
+    if (lane < 16 && col < Lr) bs_commit(colmax + col, v);
   }
 }
 
@@ -264,12 +276,12 @@ __global__ __launch_bounds__(kTThreads) void greedy_match_tiled_kernel(const T* 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int64_t col = wcol0 + 16 * j + fr;
-        if (col < Lr) v = fmaxf(v, acc[i][j][r]);
+        if (col < Lr) v = bs_max(v, acc[i][j][r]);
       }
 #pragma unroll
-      for (int off = 8; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
+      for (int off = 8; off > 0; off >>= 1) v = bs_max(v, __shfl_xor(v, off, kWave));
       const int64_t row = wrow0 + 16 * i + (lane >> 4) * 4 + r;
-      if (fr == 0 && row < Lp && v > -INFINITY) atomicMax(rmax + row, ordered_bits(v));
+      if (fr == 0 && row < Lp) bs_commit(rmax + row, v);
     }
   }
 #pragma unroll
@@ -280,12 +292,12 @@ __global__ __launch_bounds__(kTThreads) void greedy_match_tiled_kernel(const T* 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t row = wrow0 + 16 * i + (lane >> 4) * 4 + r;
-        if (row < Lp) v = fmaxf(v, acc[i][j][r]);
+        if (row < Lp) v = bs_max(v, acc[i][j][r]);
       }
-    v = fmaxf(v, __shfl_xor(v, 16, kWave));
-    v = fmaxf(v, __shfl_xor(v, 32, kWave));
+    v = bs_max(v, __shfl_xor(v, 16, kWave));
+    v = bs_max(v, __shfl_xor(v, 32, kWave));
     const int64_t col = wcol0 + 16 * j + fr;
-    if (lane < 16 && col < Lr && v > -INFINITY) atomicMax(cmax + col, ordered_bits(v));
+    if (lane < 16 && col < Lr) bs_commit(cmax + col, v);
   }
 }
 
@@ -380,12 +392,12 @@ __global__ __launch_bounds__(kWThreads) void greedy_match_w256_kernel(const T* _
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int64_t col = wcol0 + 16 * j + fr;
-        if (col < Lr) v = fmaxf(v, acc[i][j][r]);
+        if (col < Lr) v = bs_max(v, acc[i][j][r]);
       }
 #pragma unroll
-      for (int off = 8; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
+      for (int off = 8; off > 0; off >>= 1) v = bs_max(v, __shfl_xor(v, off, kWave));
       const int64_t row = wrow0 + 16 * i + (lane >> 4) * 4 + r;
-      if (fr == 0 && row < Lp && v > -INFINITY) atomicMax(rmax + row, ordered_bits(v));
+      if (fr == 0 && row < Lp) bs_commit(rmax + row, v);
     }
   }
 #pragma unroll
@@ -396,12 +408,12 @@ __global__ __launch_bounds__(kWThreads) void greedy_match_w256_kernel(const T* _
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t row = wrow0 + 16 * i + (lane >> 4) * 4 + r;
-        if (row < Lp) v = fmaxf(v, acc[i][j][r]);
+        if (row < Lp) v = bs_max(v, acc[i][j][r]);
       }
-    v = fmaxf(v, __shfl_xor(v, 16, kWave));
-    v = fmaxf(v, __shfl_xor(v, 32, kWave));
+    v = bs_max(v, __shfl_xor(v, 16, kWave));
+    v = bs_max(v, __shfl_xor(v, 32, kWave));
     const int64_t col = wcol0 + 16 * j + fr;
-    if (lane < 16 && col < Lr && v > -INFINITY) atomicMax(cmax + col, ordered_bits(v));
+    if (lane < 16 && col < Lr) bs_commit(cmax + col, v);
   }
 }
 

@@ -6,6 +6,8 @@
 // 256-thread block streams a row once with an online (max, scaled-sum) pair per thread — one exp per element —
 // merges the pairs with 64-wide wave shuffles and LDS, and reads the target logit directly: HBM traffic is one
 // pass over the logits, nothing else is materialised.  16-byte vector loads when the row is aligned.
+// Special values follow torch.logsumexp: -inf logits are masked out (a row of nothing else gives NaN, a masked target
+// +inf), a +inf logit gives +inf (NaN when it is the target), a NaN logit gives NaN; an out-of-range target gives NaN.
 #include "common.h"
 
 namespace tmx {
@@ -19,21 +21,26 @@ struct MaxSum {
 
 template <typename A>
 __device__ __forceinline__ void ms_push(MaxSum<A>& a, A x) {
-  if (x == -INFINITY) return;  // fully masked logit: contributes exp(-inf) = 0
   if (x > a.m) {
     a.s = a.s * exp(a.m - x) + A(1);
     a.m = x;
   } else {
-    a.s += exp(x - a.m);
+    // A value equal to the maximum adds 1 without forming x - m: a second +inf stays +inf (inf - inf would be NaN).
+    // A masked (-inf) logit adds exp(-inf) = 0 under a finite maximum.  While the side is still empty (m = -inf) it
+    // counts as 1, which nothing can see: the first real logit scales s by exp(-inf - x) = 0, a merge scales an empty
+    // side by exp(-inf) = 0, and a row of nothing else ends as -inf + log s = -inf (NaN after the target's -inf).
+    // No separate test for -inf in the loop.  A NaN logit makes s NaN for good, whatever the maximum is.
+    a.s += x == a.m ? A(1) : exp(x - a.m);
   }
 }
 
 template <typename A>
 __device__ __forceinline__ MaxSum<A> ms_merge(MaxSum<A> a, MaxSum<A> b) {
-  if (b.m == -INFINITY) return a;
-  if (a.m == -INFINITY) return b;
-  const A m = a.m > b.m ? a.m : b.m;
-  return {m, a.s * exp(a.m - m) + b.s * exp(b.m - m)};
+  // The side that holds the maximum keeps its sum unscaled; equal maxima add their sums, so inf - inf never forms:
+  // two empty sides (m = -inf) stay empty, an empty side adds s * exp(-inf) = 0, two +inf maxima stay +inf.  A NaN
+  // logit sits in its side's sum (never in m) and survives every scaling, 0 included.
+  if (a.m >= b.m) return {a.m, a.s + (b.m == a.m ? b.s : b.s * exp(b.m - a.m))};
+  return {b.m, b.s + a.s * exp(a.m - b.m)};
 }
 
 template <typename T> struct NllAcc { using type = float; };

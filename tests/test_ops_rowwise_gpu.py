@@ -4,7 +4,8 @@
 * multiclass hinge (crammer-singer / one-vs-all, squared, logits and probabilities): fp32 within float rounding,
   16-bit inputs within one rounding of the input dtype per row;
 * multilabel coverage / LRAP / ranking loss: exact on integer-valued (tie-heavy) scores;
-* expected mutual information (adjusted mutual info) in fp64.
+* expected mutual information (adjusted mutual info) in fp64, also against exact integer binomials;
+* macro curve interpolation called directly, against an fp64 loop and bit for bit against the fp32 per-class loop.
 """
 import pytest
 import torch
@@ -181,3 +182,128 @@ def test_macro_curve_interp_gpu_vs_cpu(C, kind):
         gpu = fn(x.cuda(), t.cuda(), num_classes=C, average="macro", thresholds=thresholds)
         for a, b in zip(gpu, cpu):
             torch.testing.assert_close(a.cpu(), b, rtol=1e-6, atol=1e-6)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Edge cases against the independent oracles of tests/helpers/oracles.py (exact integers / fp64 loops).
+import functools  # noqa: E402
+import math  # noqa: E402
+
+import numpy as np  # noqa: E402
+
+from tests.helpers import oracles as O  # noqa: E402
+
+
+def _emi_case(name):
+    if name == "table-9x13":  # the table of the test above
+        cont = torch.randint(0, 50, (9, 13), generator=torch.Generator().manual_seed(0))
+        return cont.sum(1).tolist(), cont.sum(0).tolist()
+    if name == "130x130-grid-stride":  # 16,900 pairs: more than the 4096 blocks x 4 waves of the capped grid
+        a = torch.randint(1, 20, (130,), generator=torch.Generator().manual_seed(1))
+        return a.tolist(), a[torch.randperm(130, generator=torch.Generator().manual_seed(2))].tolist()
+    return {
+        "lo>1-long-ranges": ([150000, 50000], [120000, 80000]),  # a_i + b_j > N, ranges of 5 * 10^4 values of n_ij
+        "zero-marginal": ([30, 0, 20], [25, 0, 25]),
+        "one-row": ([50], [20, 30]),
+        "marginal-equals-N": ([50, 0], [20, 30]),
+    }[name]
+
+
+@functools.lru_cache(maxsize=None)
+def _emi_reference(name):
+    a, b = _emi_case(name)
+    return O.emi_exact(a, b, sum(a))
+
+
+@pytest.mark.parametrize("name", ["table-9x13", "130x130-grid-stride", "lo>1-long-ranges", "zero-marginal", "one-row",
+                                  "marginal-equals-N"])
+def test_expected_mutual_info_kernel_vs_exact_oracle(name):
+    """csrc/clustering.hip against exact integer binomials.  Relative bound 64 * 2^-53 * lgamma(N + 1) (floor 1e-12):
+    every weight is exp() of a sum of lgamma terms of that size, each good to a few ulp, and the cancellation leaves
+    their absolute error in the exponent."""
+    from torchmetrics_forked_amd.ops.clustering import expected_mutual_info
+
+    a, b = _emi_case(name)
+    n = sum(a)
+    assert n == sum(b)
+    ref = _emi_reference(name)
+    got = float(expected_mutual_info(torch.tensor(a, dtype=torch.float64).cuda(), torch.tensor(b, dtype=torch.float64).cuda(), n).cpu())
+    rel = max(64 * 2.0 ** -53 * math.lgamma(n + 1), 1e-12)
+    print(f"expected_mutual_info {name}: got {got!r} exact {ref!r} rel err {abs(got - ref) / abs(ref) if ref else abs(got):.3e} bound {rel:.3e}")
+    assert abs(got - ref) <= rel * abs(ref), (got, ref)
+
+
+def _interp_classes(lengths, seed):
+    g = torch.Generator().manual_seed(seed)
+    xps, fps = [], []
+    for n in lengths:
+        xp = torch.rand(n, generator=g).sort().values
+        if n >= 5:
+            xp[2] = xp[1]  # repeated abscissa: zero denominator
+        if n == 5:
+            xp = xp[torch.tensor([0, 3, 1, 2, 4])]  # not monotone (macro PR curves): the segment is a count, not a place
+        if n >= 300:
+            xp[-3:] = xp[-3].clone()
+        xps.append(xp)
+        fps.append(torch.rand(n, generator=g) * 2 - 0.5)
+    return xps, fps
+
+
+def _interp_queries(m, xps, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.rand(m, generator=g) * 3 - 1  # a third below 0, a third above 1: outside every class's range
+    knots = torch.cat(xps) if xps else torch.zeros(0)
+    k = min(m, knots.numel())
+    x[:k] = knots[:k]  # exactly on the knots
+    return x
+
+
+@pytest.mark.parametrize("lengths,m", [([0, 1, 2, 5, 300], 1000), ([0, 1, 2, 5, 300], 0), ([0, 1, 2, 5, 300], 1), ([300], 777), ([1], 65),
+                                       ([0], 65), ([2, 0, 300, 1, 5], 1048577 + 300)])
+def test_macro_interp_kernel_direct(lengths, m):
+    """tmx::macro_interp called directly: empty and one-point classes, zero-width segments, queries outside every
+    class's range, no query at all and more queries than the capped grid has threads (4096 x 256).
+    fp64 bound per query: C * 2^-22 * max_c(|slope x| + |intercept|); and the header's claim, the same roundings in
+    the same order as the fp32 per-class loop over ``interp``, is checked bit for bit."""
+    from torchmetrics_forked_amd.ops.sort import argsort as _argsort
+    from torchmetrics_forked_amd.utilities.compute import interp
+
+    xps, fps = _interp_classes(lengths, sum(lengths) + m % 7)
+    x = _interp_queries(m, xps, m)
+    # the sorted copy, built as utilities.compute.macro_interp_sum builds it
+    lens = torch.tensor([0] + lengths, dtype=torch.long)
+    off = torch.cumsum(lens, 0).cuda()
+    xp, fp = torch.cat(xps).cuda(), torch.cat(fps).cuda()
+    cls = torch.repeat_interleave(torch.arange(len(lengths), device="cuda"), lens[1:].cuda())
+    o1 = _argsort(xp)
+    o2 = _argsort(cls[o1])
+    xs = xp[o1[o2]]
+    got = torch.ops.tmx.macro_interp(x.cuda(), xp, fp, xs, off).cpu()
+    assert got.shape == (m,) and got.dtype == torch.float32
+    if m == 0:
+        return
+    ref = O.macro_interp_fp64(x.numpy(), [t.numpy() for t in xps], [t.numpy() for t in fps])
+    scale = np.zeros(m)
+    xd = x.double().numpy()
+    for xpc, fpc in zip(xps, fps):
+        a, f = xpc.double().numpy(), fpc.double().numpy()
+        if len(a) == 1:
+            scale = np.maximum(scale, abs(f[0]))
+        if len(a) < 2:
+            continue
+        j = np.clip(np.searchsorted(np.sort(a), xd, "right") - 1, 0, len(a) - 2)
+        dx = np.where(a[j + 1] - a[j] == 0, 1.0, a[j + 1] - a[j])
+        slope = (f[j + 1] - f[j]) / dx
+        scale = np.maximum(scale, np.abs(slope * xd) + np.abs(f[j] - slope * a[j]))
+    tol = len(lengths) * 2.0 ** -22 * scale
+    err = np.abs(got.double().numpy() - ref)
+    ratio = float(np.max(err / np.maximum(tol, 1e-300)))
+    print(f"macro_interp lengths={lengths} M={m}: max err {err.max():.3e}, err/bound {ratio:.3f}")
+    assert ratio <= 1.0
+    cpu = torch.zeros(m)
+    for xpc, fpc in zip(xps, fps):
+        if xpc.numel() >= 2:
+            cpu = cpu + interp(x, xpc.clone(), fpc)
+        elif xpc.numel() == 1:
+            cpu = cpu + fpc[0]
+    assert torch.equal(got, cpu), f"{int((got != cpu).sum())} of {m} queries differ from the fp32 per-class loop"
