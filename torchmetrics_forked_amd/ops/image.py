@@ -62,3 +62,17 @@ class SsimSums(torch.autograd.Function):
 def ssim_sums(preds: Tensor, target: Tensor, w: Tensor, consts: Tensor, with_sse: bool = False) -> Tensor:
     """Differentiable per-plane SSIM / contrast-sensitivity sums of the native kernel."""
     return SsimSums.apply(preds, target, w, consts, with_sse)
+
+
+def ssim3d_sums(preds: Tensor, target: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, consts: Tensor) -> Tensor:
+    """``tmx::ssim3d_sums`` (``csrc/ssim3d.hip``): fp64 ``[2, P]`` per-volume sums of SSIM and contrast sensitivity over all
+    valid windows of ``preds`` / ``target`` ``[P, D, H, W]``; ``wd`` / ``wh`` / ``ww`` the 1-D windows of the three axes, ``consts``
+    ``(c1, c2)`` on the device.  No autograd: differentiable 5-D calls keep the composition."""
+    return torch.ops.tmx.ssim3d_sums(preds, target, wd, wh, ww, consts)
+
+
+def ssim3d_tile() -> Tuple[int, int, int]:
+    """``(rows, columns)`` of the output footprint one workgroup of the 3-D SSIM kernel owns, and the smallest strip of
+    output slices ``TMX_SSIM3D_STRIP`` can ask for."""
+    th, tw, min_strip = torch.ops.tmx.ssim3d_tile()
+    return int(th), int(tw), int(min_strip)
