@@ -1,11 +1,18 @@
 """Steady-state fast path of the multiclass exact-histogram update (``MulticlassPrecisionRecallCurve._fast_hist_update``):
 after the first GPU update the next ones call the native op directly.  Results must equal the full path's (fast path
 disabled by clearing the cache before every update) through resets, forward, state_dict round trips, ignore_index,
-softmax / probability switches, and deferred target-range errors."""
+softmax / probability switches, and deferred target-range errors.
+
+The second half counts calls (``tests/helpers/routes.py``): ``_curve_update`` on the metric class is the full path, the
+``torch.ops.tmx.curve_hist_update`` op is the launch both paths end in.  An update that grows the op's count but not
+the full path's took the fast path; "armed" alone does not show that."""
+import copy
+
 import pytest
 import torch
 
 import torchmetrics_forked_amd as tm
+from tests.helpers.routes import count_calls
 from torchmetrics_forked_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -16,7 +23,7 @@ def _need_native(device):
     ops.require()
 
 
-def _batches(C, n=2048, k=6, seed=0):
+def _batches(C, n=2048, k=6, seed=0, dtype=torch.bfloat16):
     g = torch.Generator().manual_seed(seed)
     out = []
     for i in range(k):
@@ -25,7 +32,7 @@ def _batches(C, n=2048, k=6, seed=0):
             x = x.softmax(1)  # probability batches in the middle: the speculation flips twice
         t = torch.randint(0, C, (n,), generator=g)
         t[::17] = -1
-        out.append((x.bfloat16().cuda(), t.cuda()))
+        out.append((x.to(dtype).cuda(), t.cuda()))
     return out
 
 
@@ -125,3 +132,129 @@ def test_fast_path_binary_matches_full_path(cls, dtype):
     fast.update(batches[0][0], bad)
     with pytest.raises(RuntimeError):
         fast.compute()
+
+
+# ---- which path ran --------------------------------------------------------------------------------------------------
+def _rows_match(preds, target, hist, task, *rest):
+    """Guard of the native-op spy: no kernel launches on inputs whose row counts differ (task 0: multiclass)."""
+    rows = preds.shape[0] if task == 0 else preds.numel()
+    assert rows == target.numel(), f"curve_hist_update reached with {tuple(preds.shape)} scores, {tuple(target.shape)} targets"
+
+
+def _observe(monkeypatch, cls):
+    full = count_calls(monkeypatch, cls, "_curve_update")
+    native = count_calls(monkeypatch, torch.ops.tmx, "curve_hist_update", guard=_rows_match)
+    return full, native
+
+
+def _step(obs, fn):
+    """(full-path calls, native-op calls) made by ``fn()``."""
+    full, native = obs
+    a, b = len(full), len(native)
+    fn()
+    return len(full) - a, len(native) - b
+
+
+FULL, FAST = (1, 1), (0, 1)
+
+
+def _binary_batches(n=2048, k=4, seed=0, dtype=torch.bfloat16):
+    g = torch.Generator().manual_seed(seed)
+    return [((torch.randn(n, generator=g) * 3).to(dtype).cuda(), torch.randint(0, 2, (n,), generator=g).cuda()) for _ in range(k)]
+
+
+def _make(cls, C):
+    """C = 0: the binary metric (armed only without ignore_index)."""
+    return cls().cuda() if C == 0 else cls(num_classes=C, ignore_index=-1).cuda()
+
+
+def _data(C, dtype, k=4, seed=0):
+    return _binary_batches(k=k, seed=seed, dtype=dtype) if C == 0 else _batches(C, k=k, seed=seed, dtype=dtype)
+
+
+ROUTE_CASES = [(tm.MulticlassAUROC, 10), (tm.MulticlassAUROC, 300), (tm.MulticlassAveragePrecision, 10),
+               (tm.MulticlassAveragePrecision, 300), (tm.BinaryAUROC, 0), (tm.BinaryAveragePrecision, 0)]
+# C = 300 x 2048 rows is below the lane threshold: the large-class kernel without lanes
+ROUTE_IDS = [f"{c.__name__}-C{n}" for c, n in ROUTE_CASES]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cls,C", ROUTE_CASES, ids=ROUTE_IDS)
+def test_fast_path_runs_and_rearms_after_every_state_change(monkeypatch, cls, C, dtype):
+    """The first update takes the full path and arms; every later one is one native call without the full path.  A
+    reset, a load_state_dict, a forward and a device round trip each cost exactly one full-path update (forward's own
+    update is that one: it carries the batch histogram), after which the fast path is back."""
+    obs = _observe(monkeypatch, cls)
+    batches = _data(C, dtype)
+    m = _make(cls, C)
+    assert [_step(obs, lambda: m.update(x, t)) for x, t in batches] == [FULL] + [FAST] * (len(batches) - 1)
+    x, t = batches[1]
+
+    m.reset()
+    assert [_step(obs, lambda: m.update(x, t)) for _ in range(3)] == [FULL, FAST, FAST]
+
+    m.persistent(True)
+    m.load_state_dict(copy.deepcopy(m.state_dict()))
+    assert [_step(obs, lambda: m.update(x, t)) for _ in range(3)] == [FULL, FAST, FAST]
+
+    assert _step(obs, lambda: m(x, t)) == FULL
+    assert [_step(obs, lambda: m.update(x, t)) for _ in range(2)] == [FAST, FAST]
+
+    m = m.cpu().cuda()
+    assert [_step(obs, lambda: m.update(x, t)) for _ in range(3)] == [FULL, FAST, FAST]
+
+    # same states as a metric that never takes the fast path, over the same sequence since the reset
+    slow = _make(cls, C)
+    for _ in range(3 + 3 + 1 + 2 + 3):
+        _slow(slow)
+        slow.update(x, t)
+    assert torch.equal(m.score_hist, slow.score_hist)
+    torch.testing.assert_close(m.compute(), slow.compute(), rtol=0, atol=0)
+
+
+@pytest.mark.parametrize("cls,C", [(tm.MulticlassAUROC, 10), (tm.MulticlassAUROC, 300), (tm.BinaryAUROC, 0)])
+def test_eager_validation_keeps_the_full_path(monkeypatch, cls, C):
+    obs = _observe(monkeypatch, cls)
+    batches = _data(C, torch.bfloat16)
+    m = _make(cls, C)
+    assert [_step(obs, lambda: m.update(x, t)) for x, t in batches[:2]] == [FULL, FAST]
+    monkeypatch.setenv("TMX_VALIDATION", "eager")  # (read on every update)
+    assert [_step(obs, lambda: m.update(x, t))[0] for x, t in batches] == [1] * len(batches)
+    monkeypatch.delenv("TMX_VALIDATION")
+    assert [_step(obs, lambda: m.update(x, t)) for x, t in batches[:3]][1:] == [FAST, FAST]  # fast again
+
+
+@pytest.mark.parametrize("C", [10, 300])
+def test_multiclass_pending_side_work_is_joined_and_update_stays_fast(monkeypatch, C):
+    obs = _observe(monkeypatch, tm.MulticlassAUROC)
+    batches = _data(C, torch.bfloat16)
+    m, slow = _make(tm.MulticlassAUROC, C), _make(tm.MulticlassAUROC, C)
+    assert [_step(obs, lambda: m.update(x, t)) for x, t in batches[:2]] == [FULL, FAST]
+    ran = []
+    m.__dict__["_side_event"] = lambda: ran.append(len(obs[1]))
+    before = len(obs[1])
+    assert _step(obs, lambda: m.update(*batches[2])) == FAST
+    assert ran == [before]  # the event ran once, before the launch
+    for x, t in batches[:3]:
+        _slow(slow)
+        slow.update(x, t)
+    assert torch.equal(m.score_hist, slow.score_hist)
+
+
+@pytest.mark.parametrize("cls", [tm.BinaryAUROC, tm.BinaryAveragePrecision])
+def test_binary_mismatched_shapes_raise_with_side_work_pending(monkeypatch, cls):
+    """The shape check does not depend on pending side work: the reference's error (``_check_same_shape`` raises a
+    RuntimeError for binary inputs), and no launch (the spy's guard refuses to forward a call whose scores and targets
+    differ in count)."""
+    obs = _observe(monkeypatch, cls)
+    batches = _data(0, torch.bfloat16)
+    m = _make(cls, 0)
+    assert [_step(obs, lambda: m.update(x, t)) for x, t in batches[:2]] == [FULL, FAST]
+    ran = []
+    m.__dict__["_side_event"] = lambda: ran.append(1)
+    x, t = batches[2]
+    before = len(obs[1])
+    with pytest.raises(RuntimeError, match="same shape"):
+        m.update(x, t[:-1])
+    assert len(obs[1]) == before and len(ran) <= 1
+    assert _step(obs, lambda: m.update(x, t))[1] == 1  # and the metric still works

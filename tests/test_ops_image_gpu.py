@@ -303,7 +303,12 @@ def test_ssim_mfma_vs_fp32_kernel(shape, ks, rng):
     if rng == 255.0:
         p, t = p.round(), t.round()
     c = torch.tensor([(0.01 * rng) ** 2, (0.03 * rng) ** 2, rng])
-    fast = _ssim_raw(p, t, ks, c)
+    from tests.helpers.routes import assert_route, kernels_run
+
+    box = []
+    names = kernels_run(lambda: box.append(_ssim_raw(p, t, ks, c)))
+    assert_route(names, present=["ssim_mfma_kernel"])  # else this compares the fp32 kernel with itself
+    fast = box[-1]
     ref = _ssim_raw(p, t, ks, c[:2])
     nv = (shape[1] - ks + 1) * (shape[2] - ks + 1)
     torch.testing.assert_close(fast[:2] / nv, ref[:2] / nv, rtol=0, atol=1e-6)

@@ -1,7 +1,7 @@
 """``tmx::radix_sort`` (csrc/radix.hip, ops/sort.py) against ``torch.sort(..., stable=True)`` on the host: identical
 indices (stability included) and bit-identical values for fp32 / fp64 / int32 / int64, ascending and descending,
-ties, NaN, +-inf, signed zeros, 1-D and row-batched 2-D inputs, tile edges (4096 keys per tile), the one-workgroup row kernels' limits (4096;
-16384 32-bit / 8192 64-bit keys)."""
+ties, NaN, +-inf, signed zeros, 1-D and row-batched 2-D inputs, tile edges (4096 keys per tile), the one-workgroup row kernels' limits (4096
+keys; 8192 keys of any width for the 1024-thread kernel)."""
 import pytest
 import torch
 
@@ -112,9 +112,14 @@ def test_radix_sort_single_tile_rows(dtype, descending):
 
 @pytest.mark.parametrize("descending", [False, True])
 def test_radix_sort_device_digit_plan(descending):
-    """Integer rows beyond the one-launch sort (> 524,288 keys): the multi-launch passes take their digit skips from a
-    plan decided on the device (no host read); skipped passes leave the buffers where they are."""
+    """Integer keys on the multi-launch passes (row batches beyond the one-workgroup kernels, one row beyond the
+    one-sweep limit of 2^22 keys): the passes take their digit skips from a plan decided on the device (no host read);
+    skipped passes leave the buffers where they are.  The single rows of 600,001 to 1,000,003 keys below take the
+    one-sweep kernels, which skip constant digits on the device too (``tests/test_routes_gpu.py`` pins which kernels run)."""
     g = torch.Generator().manual_seed(17)
+    _check(torch.randint(0, 1000, ((1 << 22) + 5,), generator=g), descending)  # planned: 2 of 8 int64 digits vary
+    _check(torch.randint(0, 70_000, (3, 20_001), generator=g, dtype=torch.int32), descending)  # planned rows, 3 of 4: odd pass count
+    _check(torch.full((2, 9_000), -5, dtype=torch.int64), descending)  # planned rows, every pass skipped
     _check(torch.randint(0, 1000, (600_001,), generator=g), descending)  # 2 of 8 int64 digits vary
     _check(torch.randint(0, 70_000, (1_000_003,), generator=g, dtype=torch.int32), descending)  # 3 of 4: odd pass count
     _check(torch.full((700_000,), -5, dtype=torch.int64), descending)  # every pass skipped

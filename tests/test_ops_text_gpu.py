@@ -113,8 +113,8 @@ _TILE_W = 256  # edge of the wide tile (kW in csrc/bertscore.hip)
 
 
 def _bert_route(shape, dtype, aligned=True):
-    """The kernel csrc/bertscore.hip picks for this call (mirrors its dispatch; used to label the measured errors
-    and to make sure the shape list below reaches every route)."""
+    """The kernel csrc/bertscore.hip is expected to pick for this call (labels the measured errors;
+    ``test_bert_edge_shapes_reach_every_route`` holds it against the kernels that ran)."""
     _, lp, lr, d = shape
     if dtype == torch.float32:
         return "f32"
@@ -141,9 +141,26 @@ BERT_EDGE_SHAPES = [(2, 470, 500, 40), (1, 256, 500, 72), (1, 256, 300, 72), (2,
 BERT_EDGE_CASES = [(s, True) for s in BERT_EDGE_SHAPES] + [((2, 257, 300, 40), False)]
 
 
+_BERT_KERNELS = {"f32": "greedy_match_f32_kernel", "half-fallback": "greedy_match_half_kernel",
+                 "tile128": "greedy_match_tiled_kernel", "w256": "greedy_match_w256_kernel"}
+
+
 def test_bert_edge_shapes_reach_every_route():
-    routes = {_bert_route(s, dt, al) for s, al in BERT_EDGE_CASES for dt in (torch.float32, torch.bfloat16)}
-    assert routes == {"f32", "half-fallback", "w256", "tile128"}
+    """The kernels that RAN for every edge case (profiled launches, not the restated rule): each case launches exactly
+    the one matching kernel its label names, and the cases together launch all four."""
+    from tests.helpers.routes import kernels_run
+
+    seen = set()
+    for shape, aligned in BERT_EDGE_CASES:
+        b, lp, lr, d = shape
+        for dtype in (torch.float32, torch.bfloat16, torch.float16):
+            p, r = torch.randn(b, lp, d).to(dtype), torch.randn(b, lr, d).to(dtype)
+            pd, rd = (p.cuda(), r.cuda()) if aligned else (_off_by_one_element(p), _off_by_one_element(r))
+            names = kernels_run(lambda: torch.ops.tmx.bert_greedy_match(pd, rd))
+            ran = {label for label, kernel in _BERT_KERNELS.items() if any(kernel in n for n in names)}
+            assert ran == {_bert_route(shape, dtype, aligned)}, (shape, dtype, aligned, sorted(set(names)))
+            seen |= ran
+    assert seen == set(_BERT_KERNELS)
 
 
 def _check_greedy(pq, rq, shape, dtype, aligned, what):

@@ -397,12 +397,15 @@ class _CurveMetric(Metric):
     # batch histogram replaces it and falls back to the full path, which re-arms); the host-side shape / dtype checks
     # of the reference's validation are kept inline, the target value check stays in the kernel (deferred flag).
     # multiclass: [N, C] scores, [N] targets; binary (no ignore_index): scores and targets of one shape.
+    # Order of the gates: task shape checks, the hand-over of big batches to the lanes, only then the join of pending
+    # side work (a join in front of the hand-over would serialise the lanes), the launch.  A histogram without a host
+    # row count (loaded, merged, graph-captured) is updated the same way; its bound stays unknown.
     def _arm_fast_update(self, preds: Tensor, target: Tensor) -> None:
         hist = self.score_hist if self.thresholds is None else None
         ok = (
             isinstance(hist, Tensor) and hist.is_cuda and hist.numel() > 0 and preds.is_cuda
             and preds.dtype in eng.HIST_DTYPES and self._range_hist is hist and self._code_range is not None
-            and self._rows_bound is not None and (not self.validate_args or self._deferred is not None)
+            and (not self.validate_args or self._deferred is not None)
         )
         if ok and self._task == "multiclass":
             ok = preds.ndim == 2 and target.ndim == 1 and "_spec_mode" in self.__dict__
@@ -421,7 +424,7 @@ class _CurveMetric(Metric):
         if (
             self.score_hist is not hist or d.get("_batch_sink") is not None or self._range_hist is not hist
             or type(preds) is not Tensor or type(target) is not Tensor or preds.dtype is not dtype
-            or preds.get_device() != dev or target.get_device() != dev or target.is_floating_point() or self._rows_bound is None
+            or preds.get_device() != dev or target.get_device() != dev or target.is_floating_point()
         ):
             return False
         multiclass = self._task == "multiclass"
@@ -429,22 +432,23 @@ class _CurveMetric(Metric):
             if preds.ndim != 2 or target.ndim != 1 or preds.shape[0] != target.shape[0] or preds.shape[1] != self._num:
                 return False
             if _LANES_ON and preds.numel() >= _LANE_MIN_ELEMS and preds.shape[1] >= _LANE_MIN_CLASSES:
-                return False  # the update lanes take it (_lane_update)
-        if d.get("_side_event") is not None:
-            self._join_side_work()
+                return False  # the update lanes take it (_lane_update): before the join, or every lane update joins
         elif preds.shape != target.shape:
             return False
+        if self.validate_args and validation_mode() == "eager":
+            return False
+        if d.get("_side_event") is not None:
+            self._join_side_work()  # (lanes in flight: their histogram work lands before this one's)
         err = None
         if self.validate_args:
-            if validation_mode() == "eager":
-                return False
             err = self._deferred.flag(RuntimeError, TARGET_RANGE_MSG if multiclass else BINARY_TARGET_MSG, hist.device)
         ii = self.ignore_index
         torch.ops.tmx.curve_hist_update(
             preds, target, hist, 0 if multiclass else 1, -1 if ii is None else ii, ii is not None, None, None, err,
             d["_spec_mode"] if multiclass else None, self._code_range, None, None,
         )
-        d["_rows_bound"] = self._rows_bound + (preds.shape[0] if multiclass else preds.numel())
+        if self._rows_bound is not None:  # (None: a loaded / merged histogram of unknown bin bound stays unknown)
+            d["_rows_bound"] = self._rows_bound + (preds.shape[0] if multiclass else preds.numel())
         return True
 
     # ---- forward on the exact histogram (GPU) -----------------------------------------------------------------------

@@ -310,7 +310,8 @@ def _rowmax_fused_wins(f1: Tensor, f2: Tensor) -> bool:
     work = f1.shape[0] * f2.shape[0] * f1.shape[1]
     if f1.dtype == torch.float32 and ((f1.shape[0] + 127) // 128) * ((f2.shape[0] + 127) // 128) >= 256:
         return True  # the f16-split matrix-core route (10,000^2 x 2048: 1.64 vs 3.87 ms, profiles/mifid_rowmax_r6.json)
-        return work <= (1 << 29) and f1.shape[1] <= 256
+    if f1.dtype == torch.float64:
+        return work <= (1 << 29) and f1.shape[1] <= 256  # beyond: the fp64 loop loses to the library GEMM
     if f1.dtype in (torch.bfloat16, torch.float16):
         return work <= (1 << 29)
     return work < (1 << 32) and f1.shape[1] <= 1024
