@@ -9,9 +9,9 @@
 //
 // Mapping (CDNA4, 64-wide waves): a block is 4 waves; blockIdx.y picks a 64-column tile of width W; a wave packs
 // R = 64 / W consecutive rows so every lane issues a coalesced load (D == 1 → 64 rows per wave instruction).
-// Elementwise math runs in fp32 for ≤32-bit inputs (same rounding as the eager reference ops) and fp64 for fp64;
-// accumulation is always fp64.  Each block reduces its lanes per column through LDS and writes one partial row;
-// the partials are summed with a deterministic torch reduction (no float atomics → bitwise reproducible).
+// Elementwise math of channels 5-7 runs in fp32 for ≤32-bit inputs (same rounding as the eager reference ops) and
+// fp64 for fp64; the products of channels 2-4 are formed in fp64 (exact for ≤32-bit inputs); accumulation is always
+// fp64.  Each block reduces its lanes per column through LDS and writes one partial row; the partials are summed with a deterministic torch reduction (no float atomics → bitwise reproducible).
 #include "common.h"
 
 namespace tmx {
@@ -99,11 +99,15 @@ __global__ __launch_bounds__(kRegBlock) void regression_sums_kernel(const T* __r
       C p = load_c(preds, off);
       C t = load_c(target, off);
       C d = p - t;
-      acc[0] += static_cast<double>(p);
-      acc[1] += static_cast<double>(t);
-      acc[2] += static_cast<double>(p * p);
-      acc[3] += static_cast<double>(t * t);
-      acc[4] += static_cast<double>(p * t);
+      // raw moments from the fp64 operands: a product of two ≤32-bit values is exact in fp64, so the centred moments
+      // Pearson / Concordance form as s2 − s0·mean keep their digits on data far from zero (fp32-rounded products
+      // lose (mean/std)²·2⁻²⁴ of the variance, which no accumulator gives back)
+      const double pd = static_cast<double>(p), td = static_cast<double>(t);
+      acc[0] += pd;
+      acc[1] += td;
+      acc[2] += pd * pd;
+      acc[3] += td * td;
+      acc[4] += pd * td;
       acc[5] += static_cast<double>(d * d);
       acc[6] += static_cast<double>(fabs(d));
       if constexpr (OP != kOpNone) acc[7] += static_cast<double>(reg_op<OP, C>(p, t, param, eps));

@@ -8,6 +8,200 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+# ------------------------------------------------------------------------------------------- regression
+
+REG_NONE, REG_APE, REG_SAPE, REG_SLE, REG_LOGCOSH, REG_MINKOWSKI, REG_ABS_T, REG_TWEEDIE = range(8)
+REG_EPS = 1.17e-06
+_U64 = 2.0 ** -53
+
+
+def reg_unit_roundoff(dtype: torch.dtype) -> float:
+    """Unit roundoff of the type the elementwise math runs in: fp32 for inputs of up to 32 bits, fp64 for fp64."""
+    return _U64 if dtype == torch.float64 else 2.0 ** -24
+
+
+def _reg_op_formula(op: int, p: torch.Tensor, t: torch.Tensor, param: float) -> torch.Tensor:
+    """Channel 7's elementwise error, from its definition, in the dtype of ``p`` / ``t``:
+    APE |p−t| / max(|t|, eps);  SAPE 2 |p−t| / max(|t|+|p|, eps);  SLE (log1p p − log1p t)²;
+    log-cosh log((e^d + e^−d) / 2), d = p − t;  Minkowski |p−t|^param;  |t|;
+    Tweedie deviance of power ``param``: 0 → (t−p)²;  1 → 2 (t·log(t/p) + p − t) with 0·log 0 = 0;
+    2 → 2 (log(p/t) + t/p − 1);  else 2 (max(t,0)^(2−a) / ((1−a)(2−a)) − t·p^(1−a) / (1−a) + p^(2−a) / (2−a))."""
+    d = p - t
+    if op == REG_NONE:
+        return torch.zeros_like(p)
+    if op == REG_APE:
+        return d.abs() / torch.clamp(t.abs(), min=REG_EPS)
+    if op == REG_SAPE:
+        return 2 * (d.abs() / torch.clamp(t.abs() + p.abs(), min=REG_EPS))
+    if op == REG_SLE:
+        e = torch.log1p(p) - torch.log1p(t)
+        return e * e
+    if op == REG_LOGCOSH:
+        return torch.log((torch.exp(d) + torch.exp(-d)) / 2)
+    if op == REG_MINKOWSKI:
+        return d.abs() ** param
+    if op == REG_ABS_T:
+        return t.abs()
+    if op != REG_TWEEDIE:
+        raise ValueError(f"unknown op {op}")
+    a = float(param)
+    if a == 0:
+        return (t - p) * (t - p)
+    if a == 1:
+        tlog = torch.where(t == 0, torch.zeros_like(t), t * torch.log(t / p))
+        return 2 * (tlog + p - t)
+    if a == 2:
+        return 2 * (torch.log(p / t) + t / p - 1)
+    term1 = torch.clamp(t, min=0) ** (2 - a) / ((1 - a) * (2 - a))
+    term2 = t * p ** (1 - a) / (1 - a)
+    term3 = p ** (2 - a) / (2 - a)
+    return 2 * (term1 - term2 + term3)
+
+
+def regression_table_exact(p: torch.Tensor, t: torch.Tensor, op: int = REG_NONE, param: float = 0.0):
+    """``(table, budget)``, both fp64 ``[8, D]``, of the sums (Σp, Σt, Σp², Σt², Σpt, Σ(p−t)², Σ|p−t|, Σ op(p, t)) over
+    the rows of ``p`` / ``t`` ``[N, D]``, from the values as stored upcast to fp64, and what a correct one-pass
+    implementation may differ from them by.
+
+    Budgets (N rows, u = unit roundoff of the compute type, fp64 accumulation in any order):
+      ch 0, 1     (N+2)·2⁻⁵³·Σ|x|: N−1 fp64 additions, each off by at most 2⁻⁵³ of a partial sum ≤ Σ|x|;
+      ch 2, 3, 4  (N+2)·2⁻⁵³·Σ|x·y|: the same, the products of two values of ≤ 24 bits being exact in fp64 (and the
+                  one rounding of an fp64 product taking one of the two spare units);
+      ch 5        (4u + N·2⁻⁵³)·Σd²: d and d·d are each rounded once in the compute type, (1+u)³ − 1 < 4u;
+      ch 6        (u + N·2⁻⁵³)·Σ|d|;
+      ch 7        4·Σ|eager − exact| + (4u + N·2⁻⁵³)·Σ|exact|, where ``eager`` is the same formula evaluated by the CPU
+                  in the compute type: the formula's own rounding (cancellation included) with a 4x margin, over a
+                  floor of 4u for a device libm that is good to 2 ulp."""
+    dt = torch.promote_types(p.dtype, t.dtype)
+    u = reg_unit_roundoff(dt)
+    cdt = torch.float64 if dt == torch.float64 else torch.float32
+    pc, tc = p.to(dt).to(cdt), t.to(dt).to(cdt)
+    x, y = pc.double(), tc.double()
+    n = x.shape[0]
+    d = x - y
+    exact7 = _reg_op_formula(op, x, y, param)
+    eager7 = _reg_op_formula(op, pc, tc, param).double()
+    chans = [x, y, x * x, y * y, x * y, d * d, d.abs(), exact7]
+    table = torch.stack([_fsum_cols(c) for c in chans])
+    mag = torch.stack([_fsum_cols(c.abs()) for c in chans])
+    nu = n * _U64
+    budget = torch.empty_like(table)
+    budget[:5] = (n + 2) * _U64 * mag[:5]
+    budget[5] = (4 * u + nu) * mag[5]
+    budget[6] = (u + nu) * mag[6]
+    budget[7] = 4 * _fsum_cols((eager7 - exact7).abs()) + (4 * u + nu) * mag[7]
+    return table, budget
+
+
+def _fsum_cols(v: torch.Tensor) -> torch.Tensor:
+    """Column sums of an fp64 ``[N, D]`` tensor: correctly rounded (``math.fsum``) up to 4096 elements; beyond, summed
+    row by row in the 64-bit significand of ``numpy.longdouble`` (error ≤ N·2⁻⁶⁴·Σ|v|, 2⁻¹¹ of the budgets above), which
+    keeps the cost of the oracle in numpy."""
+    a = v.numpy()
+    if a.size <= 4096 or np.finfo(np.longdouble).eps > 2.0 ** -60:
+        return torch.tensor([math.fsum(a[:, c]) for c in range(a.shape[1])], dtype=torch.float64)
+    return torch.from_numpy(np.sum(a.astype(np.longdouble), axis=0).astype(np.float64))
+
+
+def pearson_states_exact(batches: Sequence, state_dtype: torch.dtype = torch.float64):
+    """``(states, budget)`` of the streaming Pearson states after the ``(p, t)`` ``[N_b, D]`` batches: every batch's
+    centred two-pass moments in fp64, merged with Chan's formula in fp64.  ``states`` maps mean_x, mean_y, var_x, var_y,
+    corr_xy, n_total to fp64 ``[D]``; ``budget`` maps var_x, var_y, corr_xy to what an implementation that reads fp64
+    raw moments Σx, Σy, Σx², Σy², Σxy of each batch, merges in fp64 and stores the states in ``state_dtype`` may be off by:
+
+      every batch     4(N_b+2)·2⁻⁵³·Σ_b|x·y|: centring the raw moments, s2 − s0·s0/N.  s2 carries (N+2)·2⁻⁵³·Σx²
+                      (``regression_table_exact``), s0·s0/N twice the relative error of s0 on a value ≤ Σx²
+                      (Cauchy-Schwarz), and one more unit covers the roundings of the expression itself;
+      fp32 states     w_b(2|dx_b|ε_b + ε_b²) + 2⁻²³·|state| per batch, w_b = n0·N_b/(n0+N_b), dx_b = batch mean − prior
+                      mean: the merge term w·dx² sees the stored prior mean, which is off by ε_b; ε grows by 2⁻²⁴·|mean|
+                      with every stored update and shrinks by n0/n in the merge; storing the state rounds it by
+                      2⁻²⁴·|state|, taken twice.  (For corr_xy: w_b(|dx|ε_y + |dy|ε_x + ε_x·ε_y).)
+    ``budget`` also holds ε of the stored means after the last batch as mean_x, mean_y.  An empty batch changes nothing."""
+    d_cols = batches[0][0].shape[1]
+    z = lambda: torch.zeros(d_cols, dtype=torch.float64)  # noqa: E731
+    mx, my, vx, vy, cxy, n0 = z(), z(), z(), z(), z(), 0.0
+    bud = {"var_x": z(), "var_y": z(), "corr_xy": z()}
+    ex, ey = z(), z()
+    fp32 = state_dtype == torch.float32
+    u_state = 2.0 ** -24 if fp32 else _U64
+    for p, t in batches:
+        nb = p.shape[0]
+        if nb == 0:
+            continue
+        x, y = p.double(), t.double()
+        mxb, myb = _fsum_cols(x) / nb, _fsum_cols(y) / nb
+        xc, yc = x - mxb, y - myb
+        # corrected two-pass: the second term removes what the rounding of the batch mean leaves behind
+        sxc, syc = _fsum_cols(xc), _fsum_cols(yc)
+        m2x = _fsum_cols(xc * xc) - sxc ** 2 / nb
+        m2y = _fsum_cols(yc * yc) - syc ** 2 / nb
+        cb = _fsum_cols(xc * yc) - sxc * syc / nb
+        n = n0 + nb
+        dx, dy = mxb - mx, myb - my
+        w = n0 * nb / n
+        vx = vx + m2x + w * dx * dx
+        vy = vy + m2y + w * dy * dy
+        cxy = cxy + cb + w * dx * dy
+        mx = mx + dx * (nb / n)
+        my = my + dy * (nb / n)
+        raw = 4 * (nb + 2) * _U64
+        bud["var_x"] += raw * _fsum_cols(x * x)
+        bud["var_y"] += raw * _fsum_cols(y * y)
+        bud["corr_xy"] += raw * _fsum_cols((x * y).abs())
+        if fp32:
+            bud["var_x"] += w * (2 * dx.abs() * ex + ex * ex) + 2.0 ** -23 * vx.abs()
+            bud["var_y"] += w * (2 * dy.abs() * ey + ey * ey) + 2.0 ** -23 * vy.abs()
+            bud["corr_xy"] += w * (dx.abs() * ey + dy.abs() * ex + ex * ey) + 2.0 ** -23 * cxy.abs()
+        ex = ex * (n0 / n) + u_state * mx.abs()
+        ey = ey * (n0 / n) + u_state * my.abs()
+        n0 = n
+    bud["mean_x"], bud["mean_y"] = ex, ey
+    states = {"mean_x": mx, "mean_y": my, "var_x": vx, "var_y": vy, "corr_xy": cxy,
+              "n_total": torch.full((d_cols,), n0, dtype=torch.float64)}
+    return states, bud
+
+
+def pearson_from_states(st) -> torch.Tensor:
+    """Pearson's r ``corr_xy / sqrt(var_x · var_y)`` (the 1/(n−1) factors cancel) in fp64."""
+    return st["corr_xy"] / torch.sqrt(st["var_x"] * st["var_y"])
+
+
+def concordance_from_states(st) -> torch.Tensor:
+    """Lin's concordance ``2 s_xy / (s_x² + s_y² + (mean_x − mean_y)²)`` with the 1/(n−1) sample moments, in fp64."""
+    n1 = st["n_total"] - 1
+    return 2 * st["corr_xy"] / n1 / (st["var_x"] / n1 + st["var_y"] / n1 + (st["mean_x"] - st["mean_y"]) ** 2)
+
+
+def concordance_mean_slack(st, bud) -> torch.Tensor:
+    """What the rounding of the stored means may move the concordance coefficient by, relative to it: the means enter
+    through (mean_x − mean_y)² in the denominator, so (2|δ|ε + ε²) / denominator with δ = mean_x − mean_y and
+    ε = ε_x + ε_y.  It matters for a small batch with fp32 states, where the moment budgets are a few 2⁻²⁴."""
+    n1 = st["n_total"] - 1
+    delta, e = (st["mean_x"] - st["mean_y"]).abs(), bud["mean_x"] + bud["mean_y"]
+    return (2 * delta * e + e * e) / (st["var_x"] / n1 + st["var_y"] / n1 + delta * delta)
+
+
+def relative_state_budget(st, bud) -> float:
+    """Largest budget / |state| over var_x, var_y, corr_xy and the columns."""
+    return max(float((bud[k] / st[k].abs()).max()) for k in ("var_x", "var_y", "corr_xy"))
+
+
+def offset_batches(sizes: Sequence[int], d_cols: int, mean: float, std: float, dtype: torch.dtype = torch.float32, seed: int = 0,
+                   rho: float = 0.5):
+    """Batches ``(p, t)`` ``[N_b, D]`` of data that sits far from zero: both around ``mean`` with spread ``std`` and
+    correlation ``rho``; the columns differ a little in spread so that a column mix-up shows."""
+    g = torch.Generator().manual_seed(seed)
+    scale = std * (1 + torch.arange(d_cols, dtype=torch.float64) / 8)
+    out = []
+    for nb in sizes:
+        z1 = torch.randn(nb, d_cols, generator=g, dtype=torch.float64)
+        z2 = torch.randn(nb, d_cols, generator=g, dtype=torch.float64)
+        p = mean + scale * z1
+        t = mean + scale * (rho * z1 + math.sqrt(1 - rho * rho) * z2)
+        out.append((p.to(dtype), t.to(dtype)))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- text
 
 

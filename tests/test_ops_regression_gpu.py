@@ -3,6 +3,7 @@ functional/module results vs CPU."""
 import pytest
 import torch
 
+from tests.helpers import oracles
 from torchmetrics_forked_amd import ops
 from torchmetrics_forked_amd.ops import regression as K
 
@@ -93,7 +94,8 @@ def test_pearson_inplace_update_gpu():
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16, torch.float64])
 @pytest.mark.parametrize("op", range(8))
 def test_regression_sums_single_column(dtype, op):
-    """D == 1 sums (aligned and offset views, odd N) vs an fp64 CPU reference; repeated calls are bitwise equal."""
+    """D == 1 sums (aligned and offset views, odd N) vs an fp64 CPU reference; repeated calls are bitwise equal, and
+    the offset view is within the oracle's budget on all eight channels."""
     g = torch.Generator().manual_seed(op)
     N = 1_000_003
     p = (torch.rand(N + 1, generator=g) * 2 + 0.1).to(dtype)
@@ -111,6 +113,10 @@ def test_regression_sums_single_column(dtype, op):
     ref = torch.stack([pc.sum(), tc.sum(), (pc * pc).sum(), (tc * tc).sum(), (pc * tc).sum(), (d * d).sum(), d.abs().sum()])
     torch.testing.assert_close(flat[:7, 0].cpu(), ref, rtol=1e-4 if dtype != torch.float64 else 1e-10, atol=1e-6)
     assert tiled.shape == ref_tiled.shape == (8, 1)
+    assert torch.equal(tiled, ref_tiled)
+    table, budget = oracles.regression_table_exact(p[1:].unsqueeze(1), t[1:].unsqueeze(1), op, param)
+    err = (tiled.cpu() - table).abs()
+    assert (err <= budget).all(), (err / budget).reshape(-1)
 
 
 @pytest.mark.parametrize("cls", ["MeanMetric", "SumMetric", "MaxMetric", "MinMetric"])

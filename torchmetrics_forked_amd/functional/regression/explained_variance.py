@@ -17,9 +17,12 @@ def _explained_variance_update(preds: Tensor, target: Tensor) -> Tuple[int, Tens
     num_obs = preds.size(0)
     sums = fused_sums(preds, target) if preds.ndim <= 2 else None
     if sums is not None:
-        s = sums.to(_out_dtype(preds, target))
-        s = s if preds.ndim == 2 else s[:, 0]
-        return num_obs, s[1] - s[0], s[5], s[1], s[3]
+        dt = _out_dtype(preds, target)
+        sum_error = (sums[1] - sums[0]).to(dt)  # subtract the fp64 sums, then round once: Σt and Σp cancel
+        s = sums.to(dt)
+        if preds.ndim != 2:
+            s, sum_error = s[:, 0], sum_error[0]
+        return num_obs, sum_error, s[5], s[1], s[3]
     diff = target - preds
     return num_obs, torch.sum(diff, dim=0), torch.sum(diff * diff, dim=0), torch.sum(target, dim=0), torch.sum(target * target, dim=0)
 

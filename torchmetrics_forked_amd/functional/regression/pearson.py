@@ -51,22 +51,30 @@ def _pearson_corrcoef_update(
         corr_xy = (corr_xy.double() + cxy + w * dx * dy).to(dt).reshape(corr_xy.shape)
         num_prior = num_prior + num_obs
         return new_mx, new_my, var_x, var_y, corr_xy, num_prior
-    cond = num_prior.mean() > 0 or num_obs == 1
-    if cond:
-        mx_new = (num_prior * mean_x + preds.sum(0)) / (num_prior + num_obs)
-        my_new = (num_prior * mean_y + target.sum(0)) / (num_prior + num_obs)
-    else:
-        mx_new = preds.mean(0)
-        my_new = target.mean(0)
-    num_prior = num_prior + num_obs
-    if cond:
-        var_x = var_x + ((preds - mx_new) * (preds - mean_x)).sum(0)
-        var_y = var_y + ((target - my_new) * (target - mean_y)).sum(0)
-    else:
-        var_x = var_x + preds.var(0) * (num_obs - 1)
-        var_y = var_y + target.var(0) * (num_obs - 1)
-    corr_xy = corr_xy + ((preds - mx_new) * (target - mean_y)).sum(0)
-    return mx_new, my_new, var_x, var_y, corr_xy, num_prior
+    if num_obs == 0:
+        return mean_x, mean_y, var_x, var_y, corr_xy, num_prior
+    # Eager path in the inputs' dtype, the same merge as above.  The reference's recurrence
+    # ``Σ(p − mean_new)(p − mean_old)`` with ``mean_new = (n0·mean_old + Σp) / n`` is the same algebra, but in fp32 on data
+    # far from zero Σp loses the mean's last digits and the error ε of mean_new enters as ε·N·(batch mean − mean_old).
+    # Here the batch mean comes from a shifted sum (the deviations from the first row are small, so their sum keeps its
+    # digits), the batch moments are centred on it with the corrected two-pass form (an error ε of the batch mean
+    # cancels: Σxc² − (Σxc)²/N), and the means only meet in the merge term w·dx², as in the fused branch.
+    mxb = preds[0] + (preds - preds[0]).mean(0)
+    myb = target[0] + (target - target[0]).mean(0)
+    xc, yc = preds - mxb, target - myb
+    sx, sy = xc.sum(0), yc.sum(0)
+    m2x = (xc * xc).sum(0) - sx * sx / num_obs
+    m2y = (yc * yc).sum(0) - sy * sy / num_obs
+    cxy = (xc * yc).sum(0) - sx * sy / num_obs
+    n = num_prior + num_obs
+    dx, dy = mxb - mean_x, myb - mean_y
+    w = num_prior * num_obs / n
+    mx_new = mean_x + dx * (num_obs / n)
+    my_new = mean_y + dy * (num_obs / n)
+    var_x = var_x + m2x + w * dx * dx
+    var_y = var_y + m2y + w * dy * dy
+    corr_xy = corr_xy + cxy + w * dx * dy
+    return mx_new, my_new, var_x, var_y, corr_xy, n
 
 
 def _pearson_update_inplace(preds: Tensor, target: Tensor, states: Tuple[Tensor, ...], num_outputs: int) -> bool:

@@ -66,7 +66,8 @@ def regression_sums(preds: Tensor, target: Tensor, op: int = OP_NONE, param: flo
     cdt = torch.float64 if preds.dtype == torch.float64 else torch.float32
     p, t = preds.to(cdt), target.to(cdt)
     d = p - t
-    chans = [p, t, p * p, t * t, p * t, d * d, d.abs(), _eager_op(op, p, t, param)]
+    pd, td = p.double(), t.double()  # raw moments from the fp64 operands (exact products), as the kernel forms them
+    chans = [pd, td, pd * pd, td * td, pd * td, d * d, d.abs(), _eager_op(op, p, t, param)]
     return torch.stack([c.double().sum(0) for c in chans])
 
 
