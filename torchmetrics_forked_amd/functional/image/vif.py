@@ -1,12 +1,24 @@
 """Pixel-domain visual information fidelity (API parity: reference ``functional/image/vif.py:22-110``).
 
-All channels are processed in one batched pass per scale (channels folded into the batch) instead of a Python
-loop over channels."""
+GPU path (4-D fp32 / bf16 / fp16 inputs of at least 41 x 41, no autograd, ``sigma_n_sq > 0``): ``tmx::vif_sums``
+(``csrc/vif.hip``) — the four scales as fused separable-window kernels that read the ``[B, C, H, W]`` input in place as
+``B·C`` planes and return per-scale, per-plane numerator and denominator sums in fp64; the functional and
+``VisualInformationFidelity.update`` share ``_vif_plane_scores``.  Kept on the composition below: gradients, fp64, the CPU,
+``sigma_n_sq <= 0`` and ``TMX_VIF_NATIVE=0`` (the A/B knob of ``tools/vif_bench.py``, read once per process).
+
+The composition processes all channels in one batched pass per scale (channels folded into the batch) instead of a
+Python loop over channels."""
+import os
+
 import torch
 from torch import Tensor
 from torch.nn.functional import conv2d
 
+from torchmetrics_forked_amd import ops
+from torchmetrics_forked_amd.ops.image import vif_sums as _vif_sums
 from torchmetrics_forked_amd.utilities.distributed import reduce
+
+_VIF_NATIVE = os.environ.get("TMX_VIF_NATIVE", "1") != "0"
 
 
 def _filter(win_size: float, sigma: float, dtype: torch.dtype, device: torch.device) -> Tensor:
@@ -52,13 +64,34 @@ def _vif_planes(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:
     return num / den
 
 
+def _native_vif_ok(preds: Tensor, target: Tensor, sigma_n_sq: float) -> bool:
+    """Route to ``tmx::vif_sums``; everything else keeps the composition."""
+    if not (preds.is_cuda and target.is_cuda) or preds.ndim != 4 or preds.shape != target.shape:
+        return False
+    if preds.dtype != target.dtype or preds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+        return False
+    if preds.numel() == 0 or preds.size(-1) < 41 or preds.size(-2) < 41 or not sigma_n_sq > 0:
+        return False
+    return _VIF_NATIVE and ops.use_native(preds, target)
+
+
+def _vif_plane_scores(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:
+    """VIF of every plane of ``[B, C, H, W]`` inputs as ``[C·B]``, channel-major (the reference's cat of per-channel results)."""
+    b, c, h, w = preds.shape
+    if _native_vif_ok(preds, target, sigma_n_sq):
+        # planes in place, batch-major; only the [P] result is reordered
+        sums = _vif_sums(preds.contiguous().view(b * c, h, w), target.contiguous().view(b * c, h, w), sigma_n_sq).sum(0)
+        return (sums[0] / sums[1]).view(b, c).t().reshape(c * b).to(preds.dtype)
+    p = preds.transpose(0, 1).reshape(c * b, 1, h, w)
+    t = target.transpose(0, 1).reshape(c * b, 1, h, w)
+    return _vif_planes(p, t, sigma_n_sq)
+
+
 def visual_information_fidelity(preds: Tensor, target: Tensor, sigma_n_sq: float = 2.0) -> Tensor:
     if preds.size(-1) < 41 or preds.size(-2) < 41:
         raise ValueError(f"Invalid size of preds. Expected at least 41x41, but got {preds.size(-1)}x{preds.size(-2)}!")
     if target.size(-1) < 41 or target.size(-2) < 41:
         raise ValueError(f"Invalid size of target. Expected at least 41x41, but got {target.size(-1)}x{target.size(-2)}!")
-    b, c, h, w = preds.shape
-    # channel-major plane order matches the reference's cat of per-channel results
-    p = preds.transpose(0, 1).reshape(c * b, 1, h, w)
-    t = target.transpose(0, 1).reshape(c * b, 1, h, w)
-    return reduce(_vif_planes(p, t, sigma_n_sq), "elementwise_mean")
+    return reduce(_vif_plane_scores(preds, target, sigma_n_sq), "elementwise_mean")

@@ -76,3 +76,16 @@ def ssim3d_tile() -> Tuple[int, int, int]:
     output slices ``TMX_SSIM3D_STRIP`` can ask for."""
     th, tw, min_strip = torch.ops.tmx.ssim3d_tile()
     return int(th), int(tw), int(min_strip)
+
+
+def vif_sums(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:
+    """``tmx::vif_sums`` (``csrc/vif.hip``): fp64 ``[4, 2, P]``, per scale and per plane of ``preds`` / ``target`` ``[P, H, W]`` the sums
+    over all valid windows of the VIF-p numerator ``log10(1 + g² σt² / (σv² + σn²))`` and denominator ``log10(1 + σt² / σn²)``.
+    fp32 / bf16 / fp16 planes of at least 41 x 41, ``sigma_n_sq > 0``.  No autograd: differentiable calls keep the composition."""
+    return torch.ops.tmx.vif_sums(preds, target, float(sigma_n_sq))
+
+
+def vif_tile() -> Tuple[int, int]:
+    """``(rows, columns)`` of the output footprint one workgroup of the VIF scale kernel owns."""
+    th, tw = torch.ops.tmx.vif_tile()
+    return int(th), int(tw)
