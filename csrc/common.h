@@ -10,6 +10,7 @@
 #include <torch/library.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "device_common.h"
 
@@ -24,6 +25,32 @@ inline hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
   } while (0)
 
 #define TMX_LAUNCH_CHECK() TMX_CHECK_HIP(hipGetLastError())
+
+// Calls f(std::integral_constant<int, KS>{}) for the odd window sizes the window kernels are instantiated for.
+template <typename F>
+void dispatch_odd_window(int64_t ks, const char* name, F&& f) {
+  switch (ks) {
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    case 9: f(std::integral_constant<int, 9>{}); break;
+    case 11: f(std::integral_constant<int, 11>{}); break;
+    case 13: f(std::integral_constant<int, 13>{}); break;
+    case 15: f(std::integral_constant<int, 15>{}); break;
+    default: TORCH_CHECK(false, name, ": unsupported window size ", ks);
+  }
+}
+
+// Calls f(T{}) for the element type of an fp32 / bf16 / fp16 tensor (no fp64 instantiation, unlike TMX_DISPATCH_FLOAT).
+template <typename F>
+void dispatch_float3(at::ScalarType dtype, const char* name, F&& f) {
+  switch (dtype) {
+    case at::kFloat: f(float{}); break;
+    case at::kBFloat16: f(__hip_bfloat16{}); break;
+    case at::kHalf: f(__half{}); break;
+    default: TORCH_CHECK(false, name, ": unsupported dtype ", dtype);
+  }
+}
 
 }  // namespace tmx
 

@@ -31,7 +31,6 @@ __global__ __launch_bounds__(kSsimThreads) void ssim_valid_kernel(const T* __res
   __shared__ float sp[2][kSeg];
   __shared__ float st[2][kSeg];
   __shared__ float s_w[KS];
-  __shared__ double red[2][kSsimThreads / kWave];
 
   const int Hv = H - KS + 1, Wv = W - KS + 1;
   const int64_t plane = blockIdx.z;
@@ -107,11 +106,8 @@ __global__ __launch_bounds__(kSsimThreads) void ssim_valid_kernel(const T* __res
 #pragma unroll
             for (int q = 0; q < 5; ++q) m[q] = fmaf(wyr[k], ring[slot][q], m[q]);
           }
-          const float mu_pp = m[0] * m[0], mu_tt = m[1] * m[1], mu_pt = m[0] * m[1];
-          const float upper = 2.f * (m[4] - mu_pt) + c2;
-          const float lower = (m[2] - mu_pp) + (m[3] - mu_tt) + c2;
-          const float cs = upper / lower;
-          const float sim = (2.f * mu_pt + c1) * upper / ((mu_pp + mu_tt + c1) * lower);
+          float sim, cs;
+          ssim_finish_ieee(ssim_terms(m[0], m[1], m[2], m[3], m[4], c2), c1, sim, cs);
           acc_sim += static_cast<double>(sim);
           acc_cs += static_cast<double>(cs);
         }
@@ -120,7 +116,8 @@ __global__ __launch_bounds__(kSsimThreads) void ssim_valid_kernel(const T* __res
     }
   }
 
-  // block reduction of the two sums
+  // block reduction of the two sums (written out: block_sum_store here changes the SGPR spills at KS 13 and 15)
+  __shared__ double red[2][kSsimThreads / kWave];
   acc_sim = wave_sum(acc_sim);
   acc_cs = wave_sum(acc_cs);
   const int wave = tid / kWave, lane = tid & (kWave - 1);
@@ -217,15 +214,9 @@ at::Tensor ssim_sums(const at::Tensor& preds_in, const at::Tensor& target_in, co
                          mc.data_ptr<double>(), nullptr, flag.data_ptr<int>());
     TMX_LAUNCH_CHECK();
     // the fallback launch: every workgroup exits at its first load unless the kernel above flagged the batch
-    switch (KS) {
-      case 3: launch_ssim_v2<3>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>()); break;
-      case 5: launch_ssim_v2<5>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>()); break;
-      case 7: launch_ssim_v2<7>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>()); break;
-      case 9: launch_ssim_v2<9>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>()); break;
-      case 11: launch_ssim_v2<11>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>()); break;
-      case 13: launch_ssim_v2<13>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>()); break;
-      default: launch_ssim_v2<15>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>()); break;
-    }
+    dispatch_odd_window(KS, "ssim_sums", [&](auto ks) {
+      launch_ssim_v2<decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>());
+    });
     TMX_LAUNCH_CHECK();
     auto use_v2 = flag.gt(0);
     auto fast = with_sse ? at::stack({ms.sum(1), mc.sum(1), me.sum(1)}) : at::stack({ms.sum(1), mc.sum(1)});
@@ -233,30 +224,13 @@ at::Tensor ssim_sums(const at::Tensor& preds_in, const at::Tensor& target_in, co
     return at::where(use_v2, slow, fast);
   }
   if (v2) {
-    switch (KS) {
-      case 3: launch_ssim_v2<3>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); break;
-      case 5: launch_ssim_v2<5>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); break;
-      case 7: launch_ssim_v2<7>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); break;
-      case 9: launch_ssim_v2<9>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); break;
-      case 11: launch_ssim_v2<11>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); break;
-      case 13: launch_ssim_v2<13>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); break;
-      default: launch_ssim_v2<15>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); break;
-    }
+    dispatch_odd_window(KS, "ssim_sums", [&](auto ks) { launch_ssim_v2<decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); });
     TMX_LAUNCH_CHECK();
     if (with_sse) return at::stack({ps.sum(1), pc.sum(1), pe_t.sum(1)});
     return at::stack({ps.sum(1), pc.sum(1)});
   }
   TMX_DISPATCH_FLOAT(p.scalar_type(), "ssim_sums", [&] {
-    switch (KS) {
-      case 3: launch_ssim<scalar_t, 3>(p, t, wx, wy, consts, ps, pc, grid, H, W); break;
-      case 5: launch_ssim<scalar_t, 5>(p, t, wx, wy, consts, ps, pc, grid, H, W); break;
-      case 7: launch_ssim<scalar_t, 7>(p, t, wx, wy, consts, ps, pc, grid, H, W); break;
-      case 9: launch_ssim<scalar_t, 9>(p, t, wx, wy, consts, ps, pc, grid, H, W); break;
-      case 11: launch_ssim<scalar_t, 11>(p, t, wx, wy, consts, ps, pc, grid, H, W); break;
-      case 13: launch_ssim<scalar_t, 13>(p, t, wx, wy, consts, ps, pc, grid, H, W); break;
-      case 15: launch_ssim<scalar_t, 15>(p, t, wx, wy, consts, ps, pc, grid, H, W); break;
-      default: TORCH_CHECK(false, "ssim_sums: unsupported window size ", KS);
-    }
+    dispatch_odd_window(KS, "ssim_sums", [&](auto ks) { launch_ssim<scalar_t, decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, grid, H, W); });
   });
   TMX_LAUNCH_CHECK();
   if (with_sse) {  // (v1 path) SSE by a separate reduction
@@ -274,6 +248,18 @@ at::Tensor ssim_sums(const at::Tensor& preds_in, const at::Tensor& target_in, co
 // partial per block, summed deterministically on the host side of the op.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int kLpipsThreads = 256;
+
+// S00/a² + S11/b² − 2·S01/(a·b) of one pixel from its channel sums
+__device__ __forceinline__ double lpips_pixel(float n0, float n1, float s00, float s11, float s01) {
+  const float a2 = 1e-8f + n0, b2 = 1e-8f + n1;
+  return static_cast<double>(s00 / a2 + s11 / b2 - 2.f * s01 / (sqrtf(a2) * sqrtf(b2)));
+}
+
+// one fp64 partial per block, at [image b][blockIdx.x]
+__device__ __forceinline__ void lpips_block_store(double v, double* partial, int64_t b) {
+  double acc[1] = {v};
+  block_sum_store<1, kLpipsThreads>(acc, {partial}, [&] { return b * gridDim.x + blockIdx.x; });
+}
 
 template <typename T>
 __global__ __launch_bounds__(kLpipsThreads) void lpips_head_kernel(const T* __restrict__ f0, const T* __restrict__ f1,
@@ -296,19 +282,9 @@ __global__ __launch_bounds__(kLpipsThreads) void lpips_head_kernel(const T* __re
       s11 = fmaf(wc * y, y, s11);
       s01 = fmaf(wc * x, y, s01);
     }
-    const float a2 = 1e-8f + n0, b2 = 1e-8f + n1;
-    v = static_cast<double>(s00 / a2 + s11 / b2 - 2.f * s01 / (sqrtf(a2) * sqrtf(b2)));
+    v = lpips_pixel(n0, n1, s00, s11, s01);
   }
-  v = wave_sum(v);
-  __shared__ double red[kLpipsThreads / kWave];
-  const int wave = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) red[wave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < kLpipsThreads / kWave; ++i) t += red[i];
-    partial[b * gridDim.x + blockIdx.x] = t;
-  }
+  lpips_block_store(v, partial, b);
 }
 
 // channels_last feature maps ([B][H·W][C] in memory, what a channels_last trunk produces): the same sums, each thread
@@ -334,19 +310,9 @@ __global__ __launch_bounds__(kLpipsThreads) void lpips_head_nhwc_kernel(const T*
       s11 = fmaf(wc * y, y, s11);
       s01 = fmaf(wc * x, y, s01);
     }
-    const float a2 = 1e-8f + n0, b2 = 1e-8f + n1;
-    v = static_cast<double>(s00 / a2 + s11 / b2 - 2.f * s01 / (sqrtf(a2) * sqrtf(b2)));
+    v = lpips_pixel(n0, n1, s00, s11, s01);
   }
-  v = wave_sum(v);
-  __shared__ double red[kLpipsThreads / kWave];
-  const int wave = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) red[wave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < kLpipsThreads / kWave; ++i) t += red[i];
-    partial[b * gridDim.x + blockIdx.x] = t;
-  }
+  lpips_block_store(v, partial, b);
 }
 
 // channels_last, C % 4 == 0, 16-B aligned: four threads per pixel read adjacent float4s of its channel row (a wave covers
@@ -384,19 +350,9 @@ __global__ __launch_bounds__(kLpipsThreads) void lpips_head_nhwc4_kernel(const f
   }
   double v = 0.0;
   if (q == 0 && s < HW) {
-    const float a2 = 1e-8f + n0, b2 = 1e-8f + n1;
-    v = static_cast<double>(s00 / a2 + s11 / b2 - 2.f * s01 / (sqrtf(a2) * sqrtf(b2)));
+    v = lpips_pixel(n0, n1, s00, s11, s01);
   }
-  v = wave_sum(v);
-  __shared__ double red[kLpipsThreads / kWave];
-  const int wave = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) red[wave] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < kLpipsThreads / kWave; ++i) t += red[i];
-    partial[b * gridDim.x + blockIdx.x] = t;
-  }
+  lpips_block_store(v, partial, b);
 }
 
 // f0/f1 [B, C, H, W]; w [C] (1×1 conv weight). Returns fp64 [B] spatial means of the weighted normalised distance.

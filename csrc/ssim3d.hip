@@ -30,13 +30,12 @@
 // slice r, and the W pass of slice r + 1 follows the barrier that every thread reaches after its H pass of slice r.
 // One fp64 partial pair per workgroup, folded by a sum on the host side of the op: no atomics, deterministic.
 #include "common.h"
+#include "window_moments.h"
 
 #include <cstdlib>
 #include <vector>
 
 namespace tmx {
-
-typedef float s3f2 __attribute__((ext_vector_type(2)));
 
 constexpr int kS3Threads = 256;
 #ifndef TMX_SSIM3D_TH  // (compile-time A/B of the footprint: tools/ssim3d_bench.py --op-lib; TH x TW must stay 256)
@@ -59,12 +58,11 @@ __global__ __launch_bounds__(kS3Threads) void ssim3d_kernel(const T* __restrict_
                                                             int tiles_w, const float* __restrict__ wd, const float* __restrict__ wh,
                                                             const float* __restrict__ ww, const float* __restrict__ consts,
                                                             double* __restrict__ part_sim, double* __restrict__ part_cs) {
-  __shared__ s3f2 s_pt[kS3MaxRows * kS3MaxSeg];
-  __shared__ s3f2 s_m01[kS3MaxRows * kS3TW];
-  __shared__ s3f2 s_m23[kS3MaxRows * kS3TW];
+  __shared__ f2 s_pt[kS3MaxRows * kS3MaxSeg];
+  __shared__ f2 s_m01[kS3MaxRows * kS3TW];
+  __shared__ f2 s_m23[kS3MaxRows * kS3TW];
   __shared__ float s_m4[kS3MaxRows * kS3TW];
   __shared__ float s_wh[kS3MaxKS], s_ww[kS3MaxKS];
-  __shared__ double red[2][kS3Threads / kWave];
 
   const int tid = threadIdx.x;
   unsigned b = blockIdx.x;
@@ -113,12 +111,12 @@ __global__ __launch_bounds__(kS3Threads) void ssim3d_kernel(const T* __restrict_
   };
 
   // ring of H·W-filtered moments of the last KSD slices: (mu_p, mu_t), (E[pp], E[tt]) packed, E[pt] scalar
-  s3f2 rm[KSD], rq[KSD];
+  f2 rm[KSD], rq[KSD];
   float rx[KSD];
 #pragma unroll
   for (int k = 0; k < KSD; ++k) {
-    rm[k] = s3f2{0.f, 0.f};
-    rq[k] = s3f2{0.f, 0.f};
+    rm[k] = f2{0.f, 0.f};
+    rq[k] = f2{0.f, 0.f};
     rx[k] = 0.f;
   }
   const int ty = tid / kS3TW, tx = tid % kS3TW;
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(kS3Threads) void ssim3d_kernel(const T* __restrict_
 #pragma unroll
         for (int i = 0; i < kS3StagePer; ++i) {
           const int e = tid + i * kS3Threads;
-          if (e < n_stage) s_pt[e] = s3f2{pre_p[i], pre_t[i]};
+          if (e < n_stage) s_pt[e] = f2{pre_p[i], pre_t[i]};
         }
         __syncthreads();  // tile of slice r visible; every thread has finished the H pass of slice r - 1
         if (r + 1 < in_slices) fetch(r + 1);  // in flight during this slice's arithmetic
@@ -143,56 +141,27 @@ __global__ __launch_bounds__(kS3Threads) void ssim3d_kernel(const T* __restrict_
         for (int i = 0; i < kS3RowPer; ++i) {
           const int e = tid + i * kS3Threads;
           if (e < n_row) {
-            const s3f2* src = s_pt + (e / kS3TW) * seg + (e % kS3TW);
-            s3f2 hm = s3f2{0.f, 0.f}, hq = s3f2{0.f, 0.f};
-            float hx = 0.f;
-            for (int k = 0; k < KSW; ++k) {
-              const s3f2 v = src[k];
-              const float w = s_ww[k];
-              const s3f2 wv = s3f2{w, w} * v;                 // (w p, w t)
-              hm += wv;
-              hq = __builtin_elementwise_fma(wv, v, hq);     // (w p p, w t t)
-              hx = fmaf(wv.x, v.y, hx);                      // w p t
-            }
-            s_m01[e] = hm;
-            s_m23[e] = hq;
-            s_m4[e] = hx;
+            const Moments5 h = moments5_taps(s_pt + (e / kS3TW) * seg + (e % kS3TW), KSW, [&](int k) { return s_ww[k]; });
+            s_m01[e] = h.m01;
+            s_m23[e] = h.m23;
+            s_m4[e] = h.m4;
           }
         }
         __syncthreads();  // row moments visible; the tile buffer is free for slice r + 1
         // H pass for this thread's output pixel
-        {
-          s3f2 vm = s3f2{0.f, 0.f}, vq = s3f2{0.f, 0.f};
-          float vx = 0.f;
-          for (int k = 0; k < KSH; ++k) {
-            const int idx = (ty + k) * kS3TW + tx;
-            const float w = s_wh[k];
-            const s3f2 w2 = s3f2{w, w};
-            vm = __builtin_elementwise_fma(w2, s_m01[idx], vm);
-            vq = __builtin_elementwise_fma(w2, s_m23[idx], vq);
-            vx = fmaf(w, s_m4[idx], vx);
-          }
-          rm[j] = vm;
-          rq[j] = vq;
-          rx[j] = vx;
+        Moments5 v;
+        for (int k = 0; k < KSH; ++k) {
+          const int idx = (ty + k) * kS3TW + tx;
+          v.add(s_wh[k], s_m01[idx], s_m23[idx], s_m4[idx]);
         }
+        rm[j] = v.m01;
+        rq[j] = v.m23;
+        rx[j] = v.m4;
         if (r >= KSD - 1 && px_ok) {
           // D pass: slices r - KSD + 1 .. r live in ring slot (j + 1 + k) % KSD (oldest first)
-          s3f2 m01 = s3f2{0.f, 0.f}, m23 = s3f2{0.f, 0.f};
-          float m4 = 0.f;
-#pragma unroll
-          for (int k = 0; k < KSD; ++k) {
-            const int slot = (j + 1 + k) % KSD;
-            const s3f2 w2 = s3f2{wdr[k], wdr[k]};
-            m01 = __builtin_elementwise_fma(w2, rm[slot], m01);
-            m23 = __builtin_elementwise_fma(w2, rq[slot], m23);
-            m4 = fmaf(wdr[k], rx[slot], m4);
-          }
-          const float mu_pp = m01.x * m01.x, mu_tt = m01.y * m01.y, mu_pt = m01.x * m01.y;
-          const float upper = 2.f * (m4 - mu_pt) + c2;
-          const float lower = (m23.x - mu_pp) + (m23.y - mu_tt) + c2;
-          const float cs = upper / lower;
-          const float sim = (2.f * mu_pt + c1) * upper / ((mu_pp + mu_tt + c1) * lower);
+          const Moments5 m = moments5_ring(rm, rq, rx, j, [&](int k) { return wdr[k]; });
+          float sim, cs;
+          ssim_finish_ieee(ssim_terms(m.m01.x, m.m01.y, m.m23.x, m.m23.y, m.m4, c2), c1, sim, cs);
           acc_sim += static_cast<double>(sim);
           acc_cs += static_cast<double>(cs);
         }
@@ -200,43 +169,14 @@ __global__ __launch_bounds__(kS3Threads) void ssim3d_kernel(const T* __restrict_
     }
   }
 
-  acc_sim = wave_sum(acc_sim);
-  acc_cs = wave_sum(acc_cs);
-  const int wave = tid / kWave, lane = tid & (kWave - 1);
-  if (lane == 0) {
-    red[0][wave] = acc_sim;
-    red[1][wave] = acc_cs;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double s = 0.0, c = 0.0;
-    for (int w = 0; w < kS3Threads / kWave; ++w) {
-      s += red[0][w];
-      c += red[1][w];
-    }
-    part_sim[blockIdx.x] = s;
-    part_cs[blockIdx.x] = c;
-  }
+  double acc[2] = {acc_sim, acc_cs};
+  block_sum_store<2, kS3Threads>(acc, {part_sim, part_cs}, [&] { return blockIdx.x; });
 }
 
 template <typename T, int KSD, typename... Args>
 void launch_ssim3d_ks(const at::Tensor& p, const at::Tensor& t, unsigned grid, Args... args) {
   hipLaunchKernelGGL((ssim3d_kernel<T, KSD>), dim3(grid), dim3(kS3Threads), 0, stream(), reinterpret_cast<const T*>(p.data_ptr()),
                      reinterpret_cast<const T*>(t.data_ptr()), args...);
-}
-
-template <typename T, typename... Args>
-void launch_ssim3d(int ksd, const at::Tensor& p, const at::Tensor& t, unsigned grid, Args... args) {
-  switch (ksd) {
-    case 3: launch_ssim3d_ks<T, 3>(p, t, grid, args...); break;
-    case 5: launch_ssim3d_ks<T, 5>(p, t, grid, args...); break;
-    case 7: launch_ssim3d_ks<T, 7>(p, t, grid, args...); break;
-    case 9: launch_ssim3d_ks<T, 9>(p, t, grid, args...); break;
-    case 11: launch_ssim3d_ks<T, 11>(p, t, grid, args...); break;
-    case 13: launch_ssim3d_ks<T, 13>(p, t, grid, args...); break;
-    case 15: launch_ssim3d_ks<T, 15>(p, t, grid, args...); break;
-    default: TORCH_CHECK(false, "ssim3d_sums: unsupported window size ", ksd);
-  }
 }
 
 // (footprint rows, footprint columns, smallest strip): what the tests need to build their edge shapes
@@ -292,16 +232,14 @@ at::Tensor ssim3d_sums(const at::Tensor& preds_in, const at::Tensor& target_in, 
   auto partial = at::empty({2, P, n_strips * tiles}, opts);
   double* ps = partial.data_ptr<double>();
   double* pc = ps + groups;
-  const auto launch = [&](auto tag) {
-    using T = decltype(tag);
-    launch_ssim3d<T>(static_cast<int>(KSd), p, t, static_cast<unsigned>(groups), static_cast<int>(D), static_cast<int>(H),
-                     static_cast<int>(W), static_cast<int>(KSh), static_cast<int>(KSw), static_cast<int>(strip),
-                     static_cast<int>(n_strips), static_cast<int>(tiles_h), static_cast<int>(tiles_w), wd.data_ptr<float>(),
-                     wh.data_ptr<float>(), ww.data_ptr<float>(), consts.data_ptr<float>(), ps, pc);
-  };
-  if (dtype == at::kFloat) launch(float{});
-  else if (dtype == at::kBFloat16) launch(__hip_bfloat16{});
-  else launch(__half{});
+  dispatch_float3(dtype, "ssim3d_sums", [&](auto tag) {
+    dispatch_odd_window(KSd, "ssim3d_sums", [&](auto ksd) {
+      launch_ssim3d_ks<decltype(tag), decltype(ksd)::value>(
+          p, t, static_cast<unsigned>(groups), static_cast<int>(D), static_cast<int>(H), static_cast<int>(W), static_cast<int>(KSh),
+          static_cast<int>(KSw), static_cast<int>(strip), static_cast<int>(n_strips), static_cast<int>(tiles_h), static_cast<int>(tiles_w),
+          wd.data_ptr<float>(), wh.data_ptr<float>(), ww.data_ptr<float>(), consts.data_ptr<float>(), ps, pc);
+    });
+  });
   TMX_LAUNCH_CHECK();
   return partial.sum(2);
 }

@@ -20,6 +20,7 @@
 //                       p and t.  Gather only — no atomics, the result is deterministic.
 // The planes are processed in chunks so the maps stay under a fixed scratch cap (TMX_SSIM_GRAD_SCRATCH_MB).
 #include "common.h"
+#include "window_moments.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -123,15 +124,13 @@ __global__ __launch_bounds__(kGradThreads) void ssim_coef_kernel(const T* __rest
 #pragma unroll
             for (int q = 0; q < 5; ++q) m[q] = fmaf(wyr[k], ring[slot][q], m[q]);
           }
-          const float mu_pp = m[0] * m[0], mu_tt = m[1] * m[1], mu_pt = m[0] * m[1];
-          const float upper = 2.f * (m[4] - mu_pt) + c2;
-          const float lower = (m[2] - mu_pp) + (m[3] - mu_tt) + c2;
-          const float a = 2.f * mu_pt + c1;
-          const float b = mu_pp + mu_tt + c1;
-          const float cs = upper / lower;
+          const SsimTerms s = ssim_terms(m[0], m[1], m[2], m[3], m[4], c2);
+          const float a = 2.f * s.mu_pt + c1;
+          const float b = s.mu_pp + s.mu_tt + c1;
+          const float cs = s.upper / s.lower;
           const float lum = a / b;
           const float omega = fmaf(gs, lum, gc);
-          const float ol = omega / lower;   // ω / L
+          const float ol = omega / s.lower;   // ω / L
           const float gb = gs * cs / b;     // gs·cs / B
           const int64_t o = static_cast<int64_t>(y0 + r - (KS - 1)) * Wv + (x0 + tid);
           int q = 0;
@@ -327,28 +326,12 @@ std::tuple<at::Tensor, at::Tensor> ssim_sums_backward(const at::Tensor& preds_in
   auto maps = at::empty({chunk * per_plane}, p.options().dtype(at::kFloat));
   for (int64_t p0 = 0; p0 < P; p0 += chunk) {
     const int64_t n = std::min(chunk, P - p0);
-    auto run = [&](auto tag, auto ks) {
-      using scalar_t = decltype(tag);
-      launch_ssim_grad_sides<scalar_t, decltype(ks)::value>(need_preds, need_target, p, t, wx, wy, consts, gs, gc, maps, gp, gt, p0, n,
-                                                            static_cast<int>(H), static_cast<int>(W));
-    };
-    auto by_ks = [&](auto tag) {
-      switch (KS) {
-        case 3: run(tag, std::integral_constant<int, 3>{}); break;
-        case 5: run(tag, std::integral_constant<int, 5>{}); break;
-        case 7: run(tag, std::integral_constant<int, 7>{}); break;
-        case 9: run(tag, std::integral_constant<int, 9>{}); break;
-        case 11: run(tag, std::integral_constant<int, 11>{}); break;
-        case 13: run(tag, std::integral_constant<int, 13>{}); break;
-        default: run(tag, std::integral_constant<int, 15>{}); break;
-      }
-    };
-    if (dt == at::kFloat)
-      by_ks(float{});
-    else if (dt == at::kBFloat16)
-      by_ks(__hip_bfloat16{});
-    else
-      by_ks(__half{});
+    dispatch_float3(dt, "ssim_sums_backward", [&](auto tag) {
+      dispatch_odd_window(KS, "ssim_sums_backward", [&](auto ks) {
+        launch_ssim_grad_sides<decltype(tag), decltype(ks)::value>(need_preds, need_target, p, t, wx, wy, consts, gs, gc, maps, gp, gt, p0,
+                                                                   n, static_cast<int>(H), static_cast<int>(W));
+      });
+    });
     TMX_LAUNCH_CHECK();
   }
   return {gp, gt};

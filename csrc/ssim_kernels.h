@@ -2,7 +2,7 @@
 // tools/kexp/ssim_mfma_exp.hip).  See image.hip for the op-level documentation.
 #pragma once
 
-#include "device_common.h"
+#include "window_moments.h"
 
 namespace tmx {
 
@@ -10,14 +10,13 @@ constexpr int kSsimThreads = 256;
 
 // ------------------------------------------------------------------------------------------------------------
 // fp32, W % 4 == 0, 16-B aligned planes (the common case): the same valid-window algorithm, restructured for
-// throughput (the one-row-per-barrier kernel above ran at 0.78 TB/s on 256 x 3 x 1024^2):
+// throughput (the one-row-per-barrier ssim_valid_kernel of image.hip ran at 0.78 TB/s on 256 x 3 x 1024^2):
 //   * KS input rows are staged per barrier, prefetched into registers with 16-B loads while the previous group is
 //     computed (one barrier per KS rows instead of per row);
 //   * (p, t) are interleaved in LDS as float2, so one 8-B LDS read feeds both images, and the moment arithmetic runs
 //     on packed fp32 pairs (v_pk_mul / v_pk_add / v_pk_fma): (mu_p, mu_t) and (E[pp], E[tt]) share instructions,
 //     ~4 instructions per horizontal tap and 3 per vertical tap instead of 7 and 5;
 //   * strips of kRowsV2 output rows per block halve the KS - 1 halo rows' share of the reads.
-typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr int kRowsV2 = 128;
 
 // SSE (fused PSNR of a MetricCollection{SSIM, PSNR}): every input pixel is owned by exactly one block (rows
@@ -113,19 +112,10 @@ __global__ __launch_bounds__(kSsimThreads, 2) void ssim_v2_kernel(const float* _
     for (int j = 0; j < KS; ++j) {
       const int r = g * KS + j;
       if (r < in_rows) {  // block-uniform
-        f2 hm = f2{0.f, 0.f}, hq = f2{0.f, 0.f};
-        float hx = 0.f;
-#pragma unroll
-        for (int k = 0; k < KS; ++k) {
-          const f2 v = s_pt[buf][j][tid + k];
-          const f2 wv = wx2[k] * v;                        // (w p, w t)
-          hm += wv;
-          hq = __builtin_elementwise_fma(wv, v, hq);       // (w p p, w t t)
-          hx = fmaf(wv.x, v.y, hx);                        // w p t
-        }
-        rm[j] = hm;
-        rq[j] = hq;
-        rx[j] = hx;
+        const Moments5 h = moments5_taps(&s_pt[buf][j][tid], std::integral_constant<int, KS>{}, [&](int k) { return wx2[k]; });
+        rm[j] = h.m01;
+        rq[j] = h.m23;
+        rx[j] = h.m4;
         if constexpr (SSE) {
           if (r < own_rows) {
             if (own_col) {
@@ -141,21 +131,9 @@ __global__ __launch_bounds__(kSsimThreads, 2) void ssim_v2_kernel(const float* _
           }
         }
         if (r >= KS - 1 && col_ok) {
-          f2 m01 = f2{0.f, 0.f}, m23 = f2{0.f, 0.f};
-          float m4 = 0.f;
-#pragma unroll
-          for (int k = 0; k < KS; ++k) {
-            const int slot = (j + 1 + k) % KS;  // oldest first
-            m01 = __builtin_elementwise_fma(wy2[k], rm[slot], m01);
-            m23 = __builtin_elementwise_fma(wy2[k], rq[slot], m23);
-            m4 = fmaf(wy2[k].x, rx[slot], m4);
-          }
-          const float mu_pp = m01.x * m01.x, mu_tt = m01.y * m01.y, mu_pt = m01.x * m01.y;
-          const float upper = 2.f * (m4 - mu_pt) + c2;
-          const float lower = (m23.x - mu_pp) + (m23.y - mu_tt) + c2;
-          // hardware reciprocals (1 ulp) instead of two IEEE divisions (~10 instructions each)
-          const float cs = upper * __builtin_amdgcn_rcpf(lower);
-          const float sim = (2.f * mu_pt + c1) * cs * __builtin_amdgcn_rcpf(mu_pp + mu_tt + c1);
+          const Moments5 m = moments5_ring(rm, rq, rx, j, [&](int k) { return wy2[k]; });
+          float sim, cs;
+          ssim_finish_rcp(ssim_terms(m.m01.x, m.m01.y, m.m23.x, m.m23.y, m.m4, c2), c1, sim, cs);
           f_sim += sim;  // <= kRowsV2 terms per thread in fp32, folded into fp64 per group
           f_cs += cs;
         }
@@ -170,6 +148,7 @@ __global__ __launch_bounds__(kSsimThreads, 2) void ssim_v2_kernel(const float* _
       __syncthreads();
     }
   }
+  // (written out: block_sum_store here changes the SGPR spills from KS 11 on)
   acc_sim = wave_sum(acc_sim);
   acc_cs = wave_sum(acc_cs);
   if constexpr (SSE) acc_sse = wave_sum(acc_sse);
@@ -225,9 +204,6 @@ typedef float f4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u2_t __attribute__((ext_vector_type(2)));
 constexpr int kSsimMfmaWaves = 4;    // independent waves (column tiles) per workgroup
-#ifndef TMX_SSIM_DEPTH
-#define TMX_SSIM_DEPTH 1  // input bands in flight per wave: 1 (128 VGPRs, 4 waves / SIMD) measured 2.44-2.52 vs 2.69-2.75 ms for 2
-#endif
 constexpr float kSsimMfmaQBound = 128.f;  // (p^2 + t^2) / 256 in scaled units: |p|, |t| <= 2^7.5 for the fp16 operands
 
 // two fp32 values -> (hi pair, lo pair) of packed fp16: hi = v_cvt_pk_f16_f32 (RNE), lo = RNE16(x - hi) by
@@ -312,8 +288,8 @@ __global__ __launch_bounds__(kSsimMfmaWaves * kWave) void ssim_mfma_kernel(
   // this lane's input vectors of band b: row oy0 + 16 b + i16, columns c0 + 8 g .. + 7 (W % 4 == 0: whole float4s)
   const int xc = c0 + 8 * g;
   const bool x_ok0 = xc < W, x_ok1 = xc + 4 < W;
-  float4 np0, np1, nt0, nt1;  // band b + 2 in flight (fetch)
-  float4 cp0, cp1, ct0, ct1;  // band b + 1 (arrived or arriving)
+  // one input band in flight per wave (128 VGPRs, 4 waves / SIMD): measured 2.44-2.52 ms against 2.69-2.75 ms for two
+  float4 np0, np1, nt0, nt1;  // band b + 1 in flight (fetch)
   // every lane loads (a masked lane reads the plane's first vector) and zeroes what lies outside the image: no
   // divergent loads, no stack temporaries for the selects
   auto ld = [](const float* base, int64_t o, bool ok) -> float4 {
@@ -350,28 +326,13 @@ __global__ __launch_bounds__(kSsimMfmaWaves * kWave) void ssim_mfma_kernel(
   double acc_sim = 0.0, acc_cs = 0.0, acc_sse = 0.0;
   bool bad = false;
   const f2 c1v = {c1, c1}, c2v = {c2, c2};
-#if TMX_SSIM_DEPTH == 2
-  // two bands in flight: a band's loads are issued two band computations before its use
   fetch(0);
-  cp0 = np0; cp1 = np1; ct0 = nt0; ct1 = nt1;
-  fetch(1);
-#else
-  // one band in flight (16 fewer VGPRs: 4 waves per SIMD instead of 3)
-  fetch(0);
-#endif
   auto band = [&](const int b, auto par_c) {
     constexpr int par = decltype(par_c)::value;  // b & 1
     // (p, t) pairs of the lane's 8 columns, packed as f2 {p, t}... -- the packed ops below take two columns at once
-#if TMX_SSIM_DEPTH == 2
-    const f2 P[4] = {f2{cp0.x, cp0.y}, f2{cp0.z, cp0.w}, f2{cp1.x, cp1.y}, f2{cp1.z, cp1.w}};
-    const f2 T[4] = {f2{ct0.x, ct0.y}, f2{ct0.z, ct0.w}, f2{ct1.x, ct1.y}, f2{ct1.z, ct1.w}};
-    cp0 = np0; cp1 = np1; ct0 = nt0; ct1 = nt1;
-    if (b + 2 < nb) fetch(b + 2);
-#else
     const f2 P[4] = {f2{np0.x, np0.y}, f2{np0.z, np0.w}, f2{np1.x, np1.y}, f2{np1.z, np1.w}};
     const f2 T[4] = {f2{nt0.x, nt0.y}, f2{nt0.z, nt0.w}, f2{nt1.x, nt1.y}, f2{nt1.z, nt1.w}};
     if (b + 1 < nb) fetch(b + 1);
-#endif
     float f_sse = 0.f;
     if constexpr (SSE) {
       const int y = oy0 + 16 * b + i16;

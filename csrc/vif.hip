@@ -21,13 +21,12 @@
 // 16 x 16 footprint would restage 4x) and the W pass runs over 1.5 tile rows per output row.  LDS at N = 17: 18 KiB tile
 // + 30 KiB row moments = 48 KiB, three workgroups per CU.
 #include "common.h"
+#include "window_moments.h"
 
 #include <cmath>
 #include <vector>
 
 namespace tmx {
-
-typedef float vf2 __attribute__((ext_vector_type(2)));
 
 constexpr int kVifThreads = 256;
 constexpr int kVifTH = 32, kVifTW = 32;                     // output footprint of the scale kernel
@@ -81,11 +80,10 @@ __global__ __launch_bounds__(kVifThreads) void vif_scale_kernel(const T* __restr
                                                                 double* __restrict__ part_num, double* __restrict__ part_den) {
   constexpr int kRows = kVifTH + N - 1, kSeg = kVifTW + N - 1;
   constexpr int kStage = kRows * kSeg, kRowItems = kRows * kVifTW;
-  __shared__ vf2 s_pt[kStage];
-  __shared__ vf2 s_m01[kRowItems];  // (mu_p, mu_t) after the W pass
-  __shared__ vf2 s_m23[kRowItems];  // (E[pp], E[tt])
+  __shared__ f2 s_pt[kStage];
+  __shared__ f2 s_m01[kRowItems];  // (mu_p, mu_t) after the W pass
+  __shared__ f2 s_m23[kRowItems];  // (E[pp], E[tt])
   __shared__ float s_m4[kRowItems];  // E[pt]
-  __shared__ double red[2][kVifThreads / kWave];
 
   const int tid = threadIdx.x;
   unsigned b = blockIdx.x;
@@ -101,10 +99,10 @@ __global__ __launch_bounds__(kVifThreads) void vif_scale_kernel(const T* __restr
   for (int e = tid; e < kStage; e += kVifThreads) {
     const int r = e / kSeg, c = e - r * kSeg;
     const int y = y0 + r, x = x0 + c;
-    vf2 v = vf2{0.f, 0.f};
+    f2 v = f2{0.f, 0.f};
     if (y < H && x < W) {
       const int64_t o = static_cast<int64_t>(y) * W + x;
-      v = vf2{to_f32<T>(P[o]), to_f32<T>(Tt[o])};
+      v = f2{to_f32<T>(P[o]), to_f32<T>(Tt[o])};
     }
     s_pt[e] = v;
   }
@@ -112,21 +110,10 @@ __global__ __launch_bounds__(kVifThreads) void vif_scale_kernel(const T* __restr
 
   // W pass: (tile row, output column) items
   for (int e = tid; e < kRowItems; e += kVifThreads) {
-    const vf2* src = s_pt + (e / kVifTW) * kSeg + (e % kVifTW);
-    vf2 hm = vf2{0.f, 0.f}, hq = vf2{0.f, 0.f};
-    float hx = 0.f;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      const vf2 v = src[k];
-      const float w = win.w[k];
-      const vf2 wv = vf2{w, w} * v;                // (w p, w t)
-      hm += wv;
-      hq = __builtin_elementwise_fma(wv, v, hq);  // (w p p, w t t)
-      hx = fmaf(wv.x, v.y, hx);                   // w p t
-    }
-    s_m01[e] = hm;
-    s_m23[e] = hq;
-    s_m4[e] = hx;
+    const Moments5 h = moments5_taps(s_pt + (e / kVifTW) * kSeg + (e % kVifTW), std::integral_constant<int, N>{}, [&](int k) { return win.w[k]; });
+    s_m01[e] = h.m01;
+    s_m23[e] = h.m23;
+    s_m4[e] = h.m4;
   }
   __syncthreads();
 
@@ -136,42 +123,22 @@ __global__ __launch_bounds__(kVifThreads) void vif_scale_kernel(const T* __restr
 #pragma unroll
   for (int i = 0; i < kVifPer; ++i) {
     const int oy = ty + i * kVifRowStep;
-    vf2 vm = vf2{0.f, 0.f}, vq = vf2{0.f, 0.f};
-    float vx = 0.f;
+    Moments5 v;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       const int idx = (oy + k) * kVifTW + tx;
-      const float w = win.w[k];
-      const vf2 w2 = vf2{w, w};
-      vm = __builtin_elementwise_fma(w2, s_m01[idx], vm);
-      vq = __builtin_elementwise_fma(w2, s_m23[idx], vq);
-      vx = fmaf(w, s_m4[idx], vx);
+      v.add(win.w[k], s_m01[idx], s_m23[idx], s_m4[idx]);
     }
     if (y0 + oy < Hv && x0 + tx < Wv) {
       float num, den;
-      vif_pixel(vm.x, vm.y, vq.x, vq.y, vx, sigma_n_sq, num, den);
+      vif_pixel(v.m01.x, v.m01.y, v.m23.x, v.m23.y, v.m4, sigma_n_sq, num, den);
       acc_num += static_cast<double>(num);
       acc_den += static_cast<double>(den);
     }
   }
 
-  acc_num = wave_sum(acc_num);
-  acc_den = wave_sum(acc_den);
-  const int wave = tid / kWave, lane = tid & (kWave - 1);
-  if (lane == 0) {
-    red[0][wave] = acc_num;
-    red[1][wave] = acc_den;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double n = 0.0, d = 0.0;
-    for (int w = 0; w < kVifThreads / kWave; ++w) {
-      n += red[0][w];
-      d += red[1][w];
-    }
-    part_num[blockIdx.x] = n;
-    part_den[blockIdx.x] = d;
-  }
+  double acc[2] = {acc_num, acc_den};
+  block_sum_store<2, kVifThreads>(acc, {part_num, part_den}, [&] { return blockIdx.x; });
 }
 
 // out[y][x] = sum_ij w[i] w[j] in[2y + i][2x + j] for y < Ho = ceil((H − N + 1) / 2), x < Wo: the level the composition
@@ -182,8 +149,8 @@ __global__ __launch_bounds__(kVifThreads) void vif_decim_kernel(const T* __restr
                                                                 float* __restrict__ out_p, float* __restrict__ out_t) {
   constexpr int kRows = 2 * (kVifDT - 1) + N, kSeg = kRows;  // input rows 2y .. 2y + N − 1 of kVifDT outputs
   constexpr int kStage = kRows * kSeg, kRowItems = kRows * kVifDT;
-  __shared__ vf2 s_pt[kStage];
-  __shared__ vf2 s_mid[kRowItems];
+  __shared__ f2 s_pt[kStage];
+  __shared__ f2 s_mid[kRowItems];
 
   const int tid = threadIdx.x;
   unsigned b = blockIdx.x;
@@ -197,28 +164,28 @@ __global__ __launch_bounds__(kVifThreads) void vif_decim_kernel(const T* __restr
   for (int e = tid; e < kStage; e += kVifThreads) {
     const int r = e / kSeg, c = e - r * kSeg;
     const int y = 2 * y0 + r, x = 2 * x0 + c;
-    vf2 v = vf2{0.f, 0.f};
+    f2 v = f2{0.f, 0.f};
     if (y < H && x < W) {
       const int64_t o = static_cast<int64_t>(y) * W + x;
-      v = vf2{to_f32<T>(P[o]), to_f32<T>(Tt[o])};
+      v = f2{to_f32<T>(P[o]), to_f32<T>(Tt[o])};
     }
     s_pt[e] = v;
   }
   __syncthreads();
   for (int e = tid; e < kRowItems; e += kVifThreads) {
-    const vf2* src = s_pt + (e / kVifDT) * kSeg + 2 * (e % kVifDT);
-    vf2 h = vf2{0.f, 0.f};
+    const f2* src = s_pt + (e / kVifDT) * kSeg + 2 * (e % kVifDT);
+    f2 h = f2{0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < N; ++k) h = __builtin_elementwise_fma(vf2{win.w[k], win.w[k]}, src[k], h);
+    for (int k = 0; k < N; ++k) h = __builtin_elementwise_fma(f2{win.w[k], win.w[k]}, src[k], h);
     s_mid[e] = h;
   }
   __syncthreads();
   const int tx = tid % kVifDT, ty = tid / kVifDT;
   const int oy = y0 + ty, ox = x0 + tx;
   if (oy < Ho && ox < Wo) {
-    vf2 v = vf2{0.f, 0.f};
+    f2 v = f2{0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < N; ++k) v = __builtin_elementwise_fma(vf2{win.w[k], win.w[k]}, s_mid[(2 * ty + k) * kVifDT + tx], v);
+    for (int k = 0; k < N; ++k) v = __builtin_elementwise_fma(f2{win.w[k], win.w[k]}, s_mid[(2 * ty + k) * kVifDT + tx], v);
     const int64_t o = (plane * Ho + oy) * Wo + ox;
     out_p[o] = v.x;
     out_t[o] = v.y;
@@ -347,9 +314,7 @@ at::Tensor vif_sums(const at::Tensor& preds_in, const at::Tensor& target_in, dou
   const float sn = static_cast<float>(sigma_n_sq);
   double* part = partial.data_ptr<double>();
   float* lv = levels.data_ptr<float>();
-  if (dtype == at::kFloat) vif_run<float>(p, t, sn, h, w, tiles_h, tiles_w, offset, part, lv);
-  else if (dtype == at::kBFloat16) vif_run<__hip_bfloat16>(p, t, sn, h, w, tiles_h, tiles_w, offset, part, lv);
-  else vif_run<__half>(p, t, sn, h, w, tiles_h, tiles_w, offset, part, lv);
+  dispatch_float3(dtype, "vif_sums", [&](auto tag) { vif_run<decltype(tag)>(p, t, sn, h, w, tiles_h, tiles_w, offset, part, lv); });
   hipLaunchKernelGGL(vif_fold_kernel, dim3(static_cast<unsigned>(2 * kVifScales * P)), dim3(kWave), 0, stream(), part, fold,
                      static_cast<int>(P), out.data_ptr<double>());
   TMX_LAUNCH_CHECK();
