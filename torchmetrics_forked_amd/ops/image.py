@@ -89,3 +89,23 @@ def vif_tile() -> Tuple[int, int]:
     """``(rows, columns)`` of the output footprint one workgroup of the VIF scale kernel owns."""
     th, tw = torch.ops.tmx.vif_tile()
     return int(th), int(tw)
+
+
+def uqi_sums(preds: Tensor, target: Tensor, wy: Tensor, wx: Tensor, eps: float) -> Tensor:
+    """``tmx::uqi_sums`` (``csrc/uqi.hip``): fp64 ``[P]``, per plane of ``preds`` / ``target`` ``[P, H, W]`` the sum of the universal
+    image quality index over all valid windows; ``wy`` / ``wx`` the fp32 1-D windows of the H / W axis (one odd size in 3 .. 15),
+    ``eps`` the constant added to the variance term.  fp32 / bf16 / fp16.  No autograd: differentiable calls keep the composition."""
+    return torch.ops.tmx.uqi_sums(preds, target, wy, wx, float(eps))
+
+
+def uqi_band_pair_sums(x: Tensor, wy: Tensor, wx: Tensor, eps: float) -> Tensor:
+    """``tmx::uqi_band_pair_sums`` (``csrc/uqi.hip``): fp64 ``[L (L − 1) / 2, B]``, for every band pair ``(i < j)`` of ``x`` ``[B, L, H, W]`` in
+    ``torch.triu_indices(L, L, 1)`` order and every image the sum of the UQI between the two bands over all valid windows.  The
+    bands are read in place (no gathered copies); ``L < 2`` gives an empty result.  No autograd."""
+    return torch.ops.tmx.uqi_band_pair_sums(x, wy, wx, float(eps))
+
+
+def uqi_tile() -> Tuple[int, int]:
+    """``(output rows per strip, output columns per workgroup)`` of the UQI kernel."""
+    rows, cols = torch.ops.tmx.uqi_tile()
+    return int(rows), int(cols)
