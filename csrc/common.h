@@ -41,6 +41,19 @@ void dispatch_odd_window(int64_t ks, const char* name, F&& f) {
   }
 }
 
+// Calls f(std::integral_constant<int, WS>{}) for the box-window sizes 2 .. 16, even and odd (csrc/box_window.hip).
+template <typename F>
+void dispatch_box_window(int64_t ws, const char* name, F&& f) {
+  switch (ws) {
+#define TMX_BOX_WINDOW_CASE(n) case n: f(std::integral_constant<int, n>{}); break;
+    TMX_BOX_WINDOW_CASE(2) TMX_BOX_WINDOW_CASE(3) TMX_BOX_WINDOW_CASE(4) TMX_BOX_WINDOW_CASE(5) TMX_BOX_WINDOW_CASE(6)
+    TMX_BOX_WINDOW_CASE(7) TMX_BOX_WINDOW_CASE(8) TMX_BOX_WINDOW_CASE(9) TMX_BOX_WINDOW_CASE(10) TMX_BOX_WINDOW_CASE(11)
+    TMX_BOX_WINDOW_CASE(12) TMX_BOX_WINDOW_CASE(13) TMX_BOX_WINDOW_CASE(14) TMX_BOX_WINDOW_CASE(15) TMX_BOX_WINDOW_CASE(16)
+#undef TMX_BOX_WINDOW_CASE
+    default: TORCH_CHECK(false, name, ": unsupported window size ", ws);
+  }
+}
+
 // Calls f(T{}) for the element type of an fp32 / bf16 / fp16 tensor (no fp64 instantiation, unlike TMX_DISPATCH_FLOAT).
 template <typename F>
 void dispatch_float3(at::ScalarType dtype, const char* name, F&& f) {

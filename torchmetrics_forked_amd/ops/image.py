@@ -109,3 +109,35 @@ def uqi_tile() -> Tuple[int, int]:
     """``(output rows per strip, output columns per workgroup)`` of the UQI kernel."""
     rows, cols = torch.ops.tmx.uqi_tile()
     return int(rows), int(cols)
+
+
+def box_rmse_maps(
+    preds: Tensor, target: Tensor, window_size: int, crop: int, with_target_mean: bool = False
+) -> Tuple[Tensor, Tensor, Tensor]:
+    """``tmx::box_rmse_maps`` (``csrc/box_window.hip``): one fused kernel over ``preds`` / ``target`` ``[B, C, H, W]`` (fp32 / bf16 /
+    fp16, read in place) with a ``window_size x window_size`` box window (2 .. 16, even or odd) on SciPy's edge-including symmetric
+    padding.  Returns ``(rmse_map, crop_sums, target_mean)``: fp32 ``[C, H, W]`` the batch sum of ``sqrt(box mean of (t − p)²)``; fp64
+    ``[C]`` the sum of the same per-image values over the pixels at least ``crop`` away from every edge; fp32 ``[C, H, W]`` the batch sum of
+    ``(box mean of t) / window_size²`` when ``with_target_mean``, else an empty tensor.  ``crop`` is the caller's ``round(window_size / 2)``
+    (banker's rounding); ``H`` and ``W`` must exceed ``2 crop``.  Deterministic, no host read.  No autograd."""
+    return torch.ops.tmx.box_rmse_maps(preds, target, int(window_size), int(crop), bool(with_target_mean))
+
+
+def rase_fold(rmse_map: Tensor, target_sum: Tensor, total_images: Tensor, crop: int) -> Tensor:
+    """``tmx::rase_fold`` (``csrc/box_window.hip``): the relative average spectral error of the accumulated ``[C, H, W]`` maps as an fp64
+    device scalar: the mean over the pixels at least ``crop`` away from every edge of
+    ``100 / mean_c(target_sum / n) · sqrt(mean_c((rmse_map / n)²))`` with ``n = total_images`` (a one-element device tensor, read in the
+    kernel), in fp64 arithmetic."""
+    return torch.ops.tmx.rase_fold(rmse_map, target_sum, total_images, int(crop))
+
+
+def box_tile() -> Tuple[int, int]:
+    """``(output rows per strip, output columns per workgroup)`` of the box-window kernel."""
+    rows, cols = torch.ops.tmx.box_tile()
+    return int(rows), int(cols)
+
+
+def box_batch_chunks(b: int, c: int, h: int, w: int) -> int:
+    """How many batch chunks ``box_rmse_maps`` puts on the grid for a ``[b, c, h, w]`` call (a function of the shape alone).  Chunk
+    ``k`` holds the images ``k · ceil(b / chunks) ..``; each chunk adds its images in order and the chunks are added in order."""
+    return int(torch.ops.tmx.box_batch_chunks(int(b), int(c), int(h), int(w)))
