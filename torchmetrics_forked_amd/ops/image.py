@@ -141,3 +141,38 @@ def box_batch_chunks(b: int, c: int, h: int, w: int) -> int:
     """How many batch chunks ``box_rmse_maps`` puts on the grid for a ``[b, c, h, w]`` call (a function of the shape alone).  Chunk
     ``k`` holds the images ``k · ceil(b / chunks) ..``; each chunk adds its images in order and the chunks are added in order."""
     return int(torch.ops.tmx.box_batch_chunks(int(b), int(c), int(h), int(w)))
+
+
+def sam_map(preds: Tensor, target: Tensor) -> Tensor:
+    """``tmx::sam_map`` (``csrc/spectral.hip``): fp32 ``[B, H, W]``, per pixel of ``preds`` / ``target`` ``[B, C, H, W]`` (``C >= 2``; fp32 / bf16 /
+    fp16, read in place, once) the spectral angle ``acos(clamp(<p,t> / (|p| |t|), -1, 1))`` of the two band vectors.  The three sums run
+    over the bands in band order in fp64 and the cosine is formed in fp64, so bit-identical non-zero vectors give exactly 0; a zero
+    vector gives NaN in its pixel.  16-bit inputs give the bits of their fp32 up-cast.  No autograd."""
+    return torch.ops.tmx.sam_map(preds, target)
+
+
+def sam_sums(preds: Tensor, target: Tensor) -> Tensor:
+    """``tmx::sam_sums`` (``csrc/spectral.hip``): fp64 ``[B]``, per image the sum of the fp32 angles ``sam_map`` would store, without
+    writing the map: one fp64 partial per workgroup, added per image in a fixed order (no atomics: two runs are bit-equal).  A NaN
+    angle stays in its image's sum.  No host read.  No autograd."""
+    return torch.ops.tmx.sam_sums(preds, target)
+
+
+def ergas_scores(preds: Tensor, target: Tensor, ratio: float) -> Tensor:
+    """``tmx::ergas_scores`` (``csrc/spectral.hip``): fp64 ``[B]``, per image of ``preds`` / ``target`` ``[B, C, H, W]`` (fp32 / bf16 / fp16, read
+    in place, once) ``100 · ratio · sqrt(mean_c((SSE_bc / HW) / mean_t_bc²))`` with ``SSE`` the plane sum of ``(p − t)²`` and ``mean_t`` the plane
+    mean of ``target``.  Short fp32 vector sums added in fp64; the planes are split into ``ergas_chunks`` chunks on the grid and the
+    partials added in chunk order (deterministic).  A band whose target mean is 0 gives inf or NaN.  No host read.  No autograd."""
+    return torch.ops.tmx.ergas_scores(preds, target, float(ratio))
+
+
+def ergas_chunks(b: int, c: int, h: int, w: int) -> int:
+    """How many chunks ``ergas_scores`` splits every plane of a ``[b, c, h, w]`` call into (a function of the shape alone).  Only the
+    last chunk of a plane may be short."""
+    return int(torch.ops.tmx.ergas_chunks(int(b), int(c), int(h), int(w)))
+
+
+def spectral_tile() -> Tuple[int, int]:
+    """``(fp32 pixels per workgroup of the SAM kernels, least elements per ERGAS chunk)``; 16-bit inputs take twice the pixels."""
+    pixels, elements = torch.ops.tmx.spectral_tile()
+    return int(pixels), int(elements)
