@@ -26,6 +26,9 @@ inline hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 #define TMX_LAUNCH_CHECK() TMX_CHECK_HIP(hipGetLastError())
 
+// The y and z axes of a grid hold at most this many workgroups: an op whose planes sit on z launches that many per call.
+constexpr int64_t kMaxGridPlanes = 65535;
+
 // Calls f(std::integral_constant<int, KS>{}) for the odd window sizes the window kernels are instantiated for.
 template <typename F>
 void dispatch_odd_window(int64_t ks, const char* name, F&& f) {

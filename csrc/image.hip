@@ -138,25 +138,45 @@ __global__ __launch_bounds__(kSsimThreads) void ssim_valid_kernel(const T* __res
   }
 }
 
+// Grid z holds the planes, at most kMaxGridPlanes of them: a call with more is launched chunk by chunk.  Every launcher takes the
+// chunk's first plane ``p0`` and offsets the inputs and the [P, parts] partials by it (``grid.z`` = the planes of the chunk), so a
+// kernel sees its chunk as planes 0 .. and the partial layout and the order of every sum are those of a single launch.
 template <typename T, int KS>
-void launch_ssim(const at::Tensor& p, const at::Tensor& t, const at::Tensor& wx, const at::Tensor& wy,
-                 const at::Tensor& consts, at::Tensor& ps, at::Tensor& pc, dim3 grid, int H, int W) {
-  hipLaunchKernelGGL((ssim_valid_kernel<T, KS>), grid, kSsimThreads, 0, stream(), reinterpret_cast<const T*>(p.data_ptr()),
-                     reinterpret_cast<const T*>(t.data_ptr()), H, W, wx.data_ptr<float>(), wy.data_ptr<float>(),
-                     consts.data_ptr<float>(), ps.data_ptr<double>(), pc.data_ptr<double>());
+void launch_ssim(const at::Tensor& p, const at::Tensor& t, const at::Tensor& wx, const at::Tensor& wy, const at::Tensor& consts,
+                 at::Tensor& ps, at::Tensor& pc, dim3 grid, int H, int W, int64_t p0) {
+  const int64_t in_off = p0 * H * W, part_off = p0 * grid.y * grid.x;
+  hipLaunchKernelGGL((ssim_valid_kernel<T, KS>), grid, kSsimThreads, 0, stream(), reinterpret_cast<const T*>(p.data_ptr()) + in_off,
+                     reinterpret_cast<const T*>(t.data_ptr()) + in_off, H, W, wx.data_ptr<float>(), wy.data_ptr<float>(),
+                     consts.data_ptr<float>(), ps.data_ptr<double>() + part_off, pc.data_ptr<double>() + part_off);
 }
 
 template <int KS>
 void launch_ssim_v2(const at::Tensor& p, const at::Tensor& t, const at::Tensor& wx, const at::Tensor& wy, const at::Tensor& consts,
-                    at::Tensor& ps, at::Tensor& pc, double* pe, dim3 grid, int H, int W, const int* run_if = nullptr) {
+                    at::Tensor& ps, at::Tensor& pc, double* pe, dim3 grid, int H, int W, int64_t p0, const int* run_if = nullptr) {
+  const int64_t in_off = p0 * H * W, part_off = p0 * grid.y * grid.x;  // (W % 4 == 0: every chunk stays 16-B aligned)
+  const float* pp = p.data_ptr<float>() + in_off;
+  const float* tp = t.data_ptr<float>() + in_off;
   if (pe != nullptr)
-    hipLaunchKernelGGL((ssim_v2_kernel<KS, true>), grid, kSsimThreads, 0, stream(), p.data_ptr<float>(), t.data_ptr<float>(), H, W,
-                       wx.data_ptr<float>(), wy.data_ptr<float>(), consts.data_ptr<float>(), ps.data_ptr<double>(), pc.data_ptr<double>(), pe,
-                       run_if);
+    hipLaunchKernelGGL((ssim_v2_kernel<KS, true>), grid, kSsimThreads, 0, stream(), pp, tp, H, W, wx.data_ptr<float>(),
+                       wy.data_ptr<float>(), consts.data_ptr<float>(), ps.data_ptr<double>() + part_off, pc.data_ptr<double>() + part_off,
+                       pe + part_off, run_if);
   else
-    hipLaunchKernelGGL((ssim_v2_kernel<KS, false>), grid, kSsimThreads, 0, stream(), p.data_ptr<float>(), t.data_ptr<float>(), H, W,
-                       wx.data_ptr<float>(), wy.data_ptr<float>(), consts.data_ptr<float>(), ps.data_ptr<double>(), pc.data_ptr<double>(),
+    hipLaunchKernelGGL((ssim_v2_kernel<KS, false>), grid, kSsimThreads, 0, stream(), pp, tp, H, W, wx.data_ptr<float>(),
+                       wy.data_ptr<float>(), consts.data_ptr<float>(), ps.data_ptr<double>() + part_off, pc.data_ptr<double>() + part_off,
                        nullptr, run_if);
+}
+
+// output rows per workgroup strip of the matrix-core kernel (a multiple of 16; each strip re-reads a KS - 1 halo band); 1024
+// measured fastest of 256 / 512 / 1024 on the 1080p bench config (2.48 / 2.35 / 2.32 ms, tools/kexp/ssim_mfma_exp.hip)
+static int ssim_mfma_strip() {
+  static const int strip = std::getenv("TMX_SSIM_STRIP") ? std::max(16, std::atoi(std::getenv("TMX_SSIM_STRIP")) / 16 * 16) : 1024;
+  return strip;
+}
+
+// (generic kernel: output rows per block, packed-fp32 kernel: output rows per block, both: output columns per block,
+//  matrix-core kernel: rows and columns of an output tile, output columns per workgroup, output rows per strip)
+std::vector<int64_t> ssim_tile() {
+  return {kRowsPerBlock, kRowsV2, kSsimThreads, kSsimMfmaTile, kSsimMfmaTile * kSsimMfmaWaves, ssim_mfma_strip()};
 }
 
 // preds/target [P, H, W] planes (P = B*C); wx/wy fp32 [KS] window weights; consts fp32 [2] = (c1, c2) on device, or
@@ -177,14 +197,17 @@ at::Tensor ssim_sums(const at::Tensor& preds_in, const at::Tensor& target_in, co
   auto consts = consts_in.to(at::kFloat).contiguous();
   const int64_t P = p.size(0), H = p.size(1), W = p.size(2);
   TORCH_CHECK(H >= KS && W >= KS, "ssim_sums: image smaller than the window");
-  TORCH_CHECK(P <= 65535, "ssim_sums: too many planes for one launch");
+  // f(first plane, planes) per launch: one launch up to kMaxGridPlanes planes, the same grid as ever
+  auto for_plane_chunks = [&](auto&& f) {
+    for (int64_t p0 = 0; p0 < P; p0 += kMaxGridPlanes) f(p0, static_cast<unsigned>(std::min(kMaxGridPlanes, P - p0)));
+  };
   const int64_t Hv = H - KS + 1, Wv = W - KS + 1;
   static const bool v2_off = std::getenv("TMX_SSIM_V1") != nullptr;  // A/B knob (tools/ssim_bench.py)
   const bool v2 = !v2_off && p.scalar_type() == at::kFloat && W % 4 == 0 && (reinterpret_cast<uintptr_t>(p.data_ptr()) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0 && KS % 2 == 1 && KS <= 15;
   const int rows_per_block = v2 ? kRowsV2 : kRowsPerBlock;
   dim3 grid(static_cast<unsigned>((Wv + kSsimThreads - 1) / kSsimThreads),
-            static_cast<unsigned>((Hv + rows_per_block - 1) / rows_per_block), static_cast<unsigned>(P));
+            static_cast<unsigned>((Hv + rows_per_block - 1) / rows_per_block), 1);  // (z: set per plane chunk)
   auto opts = p.options().dtype(at::kDouble);
   auto ps = at::empty({P, static_cast<int64_t>(grid.y) * grid.x}, opts);
   auto pc = at::empty({P, static_cast<int64_t>(grid.y) * grid.x}, opts);
@@ -194,45 +217,57 @@ at::Tensor ssim_sums(const at::Tensor& preds_in, const at::Tensor& target_in, co
   // (consts = c1, c2, D), with ssim_v2_kernel as its device-side fallback for out-of-range data
   static const bool mfma_off = std::getenv("TMX_SSIM_V2") != nullptr;  // A/B knob (tools/ssim_bench.py)
   if (v2 && !mfma_off && consts.numel() >= 3 && KS <= 17) {
-    // output rows per workgroup strip (a multiple of 16; each strip re-reads a KS - 1 halo band); 1024 measured fastest
-    // of 256 / 512 / 1024 on the 1080p bench config (2.48 / 2.35 / 2.32 ms, tools/kexp/ssim_mfma_exp.hip)
-    static const int kStrip = std::getenv("TMX_SSIM_STRIP") ? std::max(16, std::atoi(std::getenv("TMX_SSIM_STRIP")) / 16 * 16) : 1024;
+    const int kStrip = ssim_mfma_strip();
     const int ntx = static_cast<int>((Wv + 15) / 16);
-    dim3 mgrid(static_cast<unsigned>((ntx + kSsimMfmaWaves - 1) / kSsimMfmaWaves), static_cast<unsigned>((Hv + kStrip - 1) / kStrip),
-               static_cast<unsigned>(P));
+    dim3 mgrid(static_cast<unsigned>((ntx + kSsimMfmaWaves - 1) / kSsimMfmaWaves), static_cast<unsigned>((Hv + kStrip - 1) / kStrip), 1);
     const int64_t nparts = static_cast<int64_t>(mgrid.y) * ntx;
     auto ms = at::empty({P, nparts}, opts), mc = at::empty({P, nparts}, opts);
     auto me = with_sse ? at::empty({P, nparts}, opts) : at::Tensor();
+    // one flag for the whole call: every chunk's launch can set it, and every fallback launch is enqueued after all of them
     auto flag = at::zeros({1}, p.options().dtype(at::kInt));
-    if (with_sse)
-      hipLaunchKernelGGL((ssim_mfma_kernel<true>), mgrid, kSsimMfmaWaves * kWave, 0, stream(), p.data_ptr<float>(), t.data_ptr<float>(),
-                         (int)H, (int)W, (int)KS, kStrip, wx.data_ptr<float>(), consts.data_ptr<float>(), ms.data_ptr<double>(),
-                         mc.data_ptr<double>(), me.data_ptr<double>(), flag.data_ptr<int>());
-    else
-      hipLaunchKernelGGL((ssim_mfma_kernel<false>), mgrid, kSsimMfmaWaves * kWave, 0, stream(), p.data_ptr<float>(), t.data_ptr<float>(),
-                         (int)H, (int)W, (int)KS, kStrip, wx.data_ptr<float>(), consts.data_ptr<float>(), ms.data_ptr<double>(),
-                         mc.data_ptr<double>(), nullptr, flag.data_ptr<int>());
-    TMX_LAUNCH_CHECK();
-    // the fallback launch: every workgroup exits at its first load unless the kernel above flagged the batch
-    dispatch_odd_window(KS, "ssim_sums", [&](auto ks) {
-      launch_ssim_v2<decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, flag.data_ptr<int>());
+    for_plane_chunks([&](int64_t p0, unsigned n) {
+      mgrid.z = n;
+      const int64_t in_off = p0 * H * W, part_off = p0 * nparts;  // (W % 4 == 0: every chunk stays 16-B aligned)
+      if (with_sse)
+        hipLaunchKernelGGL((ssim_mfma_kernel<true>), mgrid, kSsimMfmaWaves * kWave, 0, stream(), p.data_ptr<float>() + in_off,
+                           t.data_ptr<float>() + in_off, (int)H, (int)W, (int)KS, kStrip, wx.data_ptr<float>(), consts.data_ptr<float>(),
+                           ms.data_ptr<double>() + part_off, mc.data_ptr<double>() + part_off, me.data_ptr<double>() + part_off,
+                           flag.data_ptr<int>());
+      else
+        hipLaunchKernelGGL((ssim_mfma_kernel<false>), mgrid, kSsimMfmaWaves * kWave, 0, stream(), p.data_ptr<float>() + in_off,
+                           t.data_ptr<float>() + in_off, (int)H, (int)W, (int)KS, kStrip, wx.data_ptr<float>(), consts.data_ptr<float>(),
+                           ms.data_ptr<double>() + part_off, mc.data_ptr<double>() + part_off, nullptr, flag.data_ptr<int>());
+      TMX_LAUNCH_CHECK();
     });
-    TMX_LAUNCH_CHECK();
+    // the fallback launches: every workgroup exits at its first load unless a kernel above flagged the batch
+    for_plane_chunks([&](int64_t p0, unsigned n) {
+      grid.z = n;
+      dispatch_odd_window(KS, "ssim_sums", [&](auto ks) {
+        launch_ssim_v2<decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, p0, flag.data_ptr<int>());
+      });
+      TMX_LAUNCH_CHECK();
+    });
     auto use_v2 = flag.gt(0);
     auto fast = with_sse ? at::stack({ms.sum(1), mc.sum(1), me.sum(1)}) : at::stack({ms.sum(1), mc.sum(1)});
     auto slow = with_sse ? at::stack({ps.sum(1), pc.sum(1), pe_t.sum(1)}) : at::stack({ps.sum(1), pc.sum(1)});
     return at::where(use_v2, slow, fast);
   }
   if (v2) {
-    dispatch_odd_window(KS, "ssim_sums", [&](auto ks) { launch_ssim_v2<decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W); });
-    TMX_LAUNCH_CHECK();
+    for_plane_chunks([&](int64_t p0, unsigned n) {
+      grid.z = n;
+      dispatch_odd_window(KS, "ssim_sums", [&](auto ks) { launch_ssim_v2<decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, pe, grid, H, W, p0); });
+      TMX_LAUNCH_CHECK();
+    });
     if (with_sse) return at::stack({ps.sum(1), pc.sum(1), pe_t.sum(1)});
     return at::stack({ps.sum(1), pc.sum(1)});
   }
-  TMX_DISPATCH_FLOAT(p.scalar_type(), "ssim_sums", [&] {
-    dispatch_odd_window(KS, "ssim_sums", [&](auto ks) { launch_ssim<scalar_t, decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, grid, H, W); });
+  for_plane_chunks([&](int64_t p0, unsigned n) {
+    grid.z = n;
+    TMX_DISPATCH_FLOAT(p.scalar_type(), "ssim_sums", [&] {
+      dispatch_odd_window(KS, "ssim_sums", [&](auto ks) { launch_ssim<scalar_t, decltype(ks)::value>(p, t, wx, wy, consts, ps, pc, grid, H, W, p0); });
+    });
+    TMX_LAUNCH_CHECK();
   });
-  TMX_LAUNCH_CHECK();
   if (with_sse) {  // (v1 path) SSE by a separate reduction
     auto d = (p.to(at::kDouble) - t.to(at::kDouble));
     return at::stack({ps.sum(1), pc.sum(1), (d * d).sum({1, 2})});
@@ -402,6 +437,7 @@ at::Tensor lpips_head(const at::Tensor& f0_in, const at::Tensor& f1_in, const at
 TORCH_LIBRARY_FRAGMENT(tmx, m) {
   m.def("ssim_sums(Tensor preds, Tensor target, Tensor wx, Tensor wy, Tensor consts, bool with_sse=False) -> Tensor");
   m.def("lpips_head(Tensor f0, Tensor f1, Tensor w) -> Tensor");
+  m.def("ssim_tile() -> int[]", &tmx::ssim_tile);
 }
 
 TORCH_LIBRARY_IMPL(tmx, CUDA, m) {

@@ -299,7 +299,6 @@ std::tuple<at::Tensor, at::Tensor> ssim_sums_backward(const at::Tensor& preds_in
   TORCH_CHECK(KS % 2 == 1 && KS >= 3 && KS <= 15, "ssim_sums_backward: unsupported window size ", KS);
   const int64_t P = preds_in.size(0), H = preds_in.size(1), W = preds_in.size(2);
   TORCH_CHECK(H >= KS && W >= KS, "ssim_sums_backward: image smaller than the window");
-  TORCH_CHECK(P <= 65535, "ssim_sums_backward: too many planes for one launch");
   TORCH_CHECK(H < (int64_t{1} << 30) && W < (int64_t{1} << 30), "ssim_sums_backward: plane too large");
   TORCH_CHECK(consts_in.numel() >= 2, "ssim_sums_backward: consts holds (c1, c2[, data range])");
   TORCH_CHECK(grad_sim_in.numel() == P && grad_cs_in.numel() == P, "ssim_sums_backward: expected [P] upstream gradients");
@@ -322,7 +321,8 @@ std::tuple<at::Tensor, at::Tensor> ssim_sums_backward(const at::Tensor& preds_in
   const int64_t Hv = H - KS + 1, Wv = W - KS + 1;
   const int64_t nm = 2 + (need_preds ? 1 : 0) + (need_target ? 1 : 0);
   const int64_t per_plane = nm * Hv * Wv;  // floats
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, grad_scratch_bytes() / 4 / per_plane));
+  // (the planes of a chunk are the grid's z axis: at most kMaxGridPlanes of them, whatever the scratch would hold)
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>({P, kMaxGridPlanes, grad_scratch_bytes() / 4 / per_plane}));
   auto maps = at::empty({chunk * per_plane}, p.options().dtype(at::kFloat));
   for (int64_t p0 = 0; p0 < P; p0 += chunk) {
     const int64_t n = std::min(chunk, P - p0);

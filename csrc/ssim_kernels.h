@@ -204,6 +204,7 @@ typedef float f4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u2_t __attribute__((ext_vector_type(2)));
 constexpr int kSsimMfmaWaves = 4;    // independent waves (column tiles) per workgroup
+constexpr int kSsimMfmaTile = 16;    // rows and columns of one wave's output tile (the 16x16x32 products; written as 16 below)
 constexpr float kSsimMfmaQBound = 128.f;  // (p^2 + t^2) / 256 in scaled units: |p|, |t| <= 2^7.5 for the fp16 operands
 
 // two fp32 values -> (hi pair, lo pair) of packed fp16: hi = v_cvt_pk_f16_f32 (RNE), lo = RNE16(x - hi) by

@@ -64,6 +64,14 @@ def ssim_sums(preds: Tensor, target: Tensor, w: Tensor, consts: Tensor, with_sse
     return SsimSums.apply(preds, target, w, consts, with_sse)
 
 
+def ssim_tile() -> Tuple[int, int, int, int, int, int]:
+    """Geometry of the three 2-D SSIM kernels: ``(output rows per block of the generic kernel, output rows per block of the packed-fp32
+    kernel, output columns per block of both, rows and columns of an output tile of the matrix-core kernel, output columns per
+    workgroup of that kernel, output rows per strip of that kernel)``."""
+    rows, rows_v2, cols, tile, group_cols, strip = torch.ops.tmx.ssim_tile()
+    return int(rows), int(rows_v2), int(cols), int(tile), int(group_cols), int(strip)
+
+
 def ssim3d_sums(preds: Tensor, target: Tensor, wd: Tensor, wh: Tensor, ww: Tensor, consts: Tensor) -> Tensor:
     """``tmx::ssim3d_sums`` (``csrc/ssim3d.hip``): fp64 ``[2, P]`` per-volume sums of SSIM and contrast sensitivity over all
     valid windows of ``preds`` / ``target`` ``[P, D, H, W]``; ``wd`` / ``wh`` / ``ww`` the 1-D windows of the three axes, ``consts``
