@@ -4,8 +4,16 @@ SDR's optimal distortion filter needs the solution of an L×L symmetric Toeplitz
 materialises the Toeplitz matrix and calls a dense ``torch.linalg.solve`` (O(L³)); here the native Levinson
 recursion ``tmx::toeplitz_solve`` (O(L²), one GPU block or CPU task per signal) solves it from the autocorrelation
 vector directly.  ``use_cg_iter`` (fast-bss-eval's conjugate gradient) is accepted; the direct solve is always exact.
+
+SI-SDR and SA-SDR on the GPU (fp32 / bf16 / fp16 inputs of one dtype, no autograd) run ``tmx::signal_pair_ratios``
+(``csrc/signal_pairs.hip``): streaming passes over the signals read in place, with the means, the scale ``α`` and the residual sum
+``Σ(α t − p)²`` in fp64, so no full-size temporary is written and the result is the fp64 value of the formula rounded once to the
+input dtype.  Kept on the composition (``_si_sdr_composition`` / ``_sa_sdr_composition``): fp64 and complex inputs, gradients,
+mixed dtypes, the CPU, empty inputs and ``TMX_AUDIO_NATIVE=0`` (the A/B knob of ``tools/audio_bench.py``, read once per process).
+``signal_distortion_ratio`` itself is not routed.
 """
 import math
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -13,7 +21,34 @@ from torch import Tensor
 from torch.linalg import norm
 
 from torchmetrics_forked_amd import ops
+from torchmetrics_forked_amd.ops.audio import PAIR_AGGREGATED, PAIR_DIAGONAL
+from torchmetrics_forked_amd.ops.audio import signal_pair_ratios as _signal_pair_ratios
 from torchmetrics_forked_amd.utilities.checks import _check_same_shape
+
+_AUDIO_NATIVE = os.environ.get("TMX_AUDIO_NATIVE", "1") != "0"
+
+
+def _native_signal_ok(preds: Tensor, target: Tensor) -> bool:
+    """Route to ``tmx::signal_pair_ratios``; everything else keeps the composition."""
+    if not (preds.is_cuda and target.is_cuda):
+        return False
+    if preds.dtype != target.dtype or preds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    if preds.is_complex() or target.is_complex():
+        return False
+    if preds.ndim < 1 or preds.shape != target.shape or preds.numel() == 0:
+        return False
+    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
+        return False
+    return _AUDIO_NATIVE and ops.use_native(preds, target)
+
+
+def _native_row_ratios(preds: Tensor, target: Tensor, scale_invariant: bool, zero_mean: bool) -> Tensor:
+    """The ratio of every ``(..., T)`` row pair: the leading dims flattened to ``[rows, 1, T]``, cast to the input dtype."""
+    time = preds.shape[-1]
+    eps = torch.finfo(preds.dtype).eps
+    out = _signal_pair_ratios(preds.reshape(-1, 1, time), target.reshape(-1, 1, time), scale_invariant, zero_mean, PAIR_DIAGONAL, eps)
+    return out.to(preds.dtype).reshape(preds.shape[:-1])
 
 
 def _symmetric_toeplitz(vector: Tensor) -> Tensor:
@@ -70,6 +105,12 @@ def signal_distortion_ratio(
 def scale_invariant_signal_distortion_ratio(preds: Tensor, target: Tensor, zero_mean: bool = False) -> Tensor:
     """SI-SDR over the last dim."""
     _check_same_shape(preds, target)
+    if _native_signal_ok(preds, target):
+        return _native_row_ratios(preds, target, True, bool(zero_mean))
+    return _si_sdr_composition(preds, target, zero_mean)
+
+
+def _si_sdr_composition(preds: Tensor, target: Tensor, zero_mean: bool = False) -> Tensor:
     eps = torch.finfo(preds.dtype).eps
     if zero_mean:
         target = target - target.mean(dim=-1, keepdim=True)
@@ -87,6 +128,17 @@ def source_aggregated_signal_distortion_ratio(
     _check_same_shape(preds, target)
     if preds.ndim < 2:
         raise RuntimeError(f"The preds and target should have the shape (..., spk, time), but {preds.shape} found")
+    if _native_signal_ok(preds, target):
+        spk, time = preds.shape[-2:]
+        eps = torch.finfo(preds.dtype).eps
+        out = _signal_pair_ratios(
+            preds.reshape(-1, spk, time), target.reshape(-1, spk, time), bool(scale_invariant), bool(zero_mean), PAIR_AGGREGATED, eps
+        )
+        return out.to(preds.dtype).reshape(preds.shape[:-2])
+    return _sa_sdr_composition(preds, target, scale_invariant, zero_mean)
+
+
+def _sa_sdr_composition(preds: Tensor, target: Tensor, scale_invariant: bool = True, zero_mean: bool = False) -> Tensor:
     eps = torch.finfo(preds.dtype).eps
     if zero_mean:
         target = target - target.mean(dim=-1, keepdim=True)
