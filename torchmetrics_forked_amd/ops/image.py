@@ -184,3 +184,34 @@ def spectral_tile() -> Tuple[int, int]:
     """``(fp32 pixels per workgroup of the SAM kernels, least elements per ERGAS chunk)``; 16-bit inputs take twice the pixels."""
     pixels, elements = torch.ops.tmx.spectral_tile()
     return int(pixels), int(elements)
+
+
+def psnrb_sums(preds: Tensor, target: Tensor, block_size: int) -> Tensor:
+    """``tmx::psnrb_sums`` (``csrc/neighbour_diff.hip``): fp64 ``[5]`` = ``Σ(p − t)²``, ``D_B``, ``D_BC``, ``min target``, ``max target`` over the whole
+    ``[B, 1, H, W]`` batch (fp32 / bf16 / fp16, each input read in place, once).  ``D_B`` is the sum of the squared differences of ``preds``
+    over the horizontal pairs ``(j, j + 1)`` with ``(j + 1) % block_size == 0`` and the vertical pairs ``(i, i + 1)`` with ``(i + 1) % block_size == 0``,
+    ``D_BC`` the same over every other pair; an empty set adds 0.  The differences are fp32, their squares are added in fp64: one
+    partial per workgroup, added in a fixed order (no atomics: two runs are bit-equal).  Minimum and maximum give NaN where
+    ``target`` holds one.  16-bit inputs give the bits of their fp32 up-cast.  No host read.  No autograd."""
+    return torch.ops.tmx.psnrb_sums(preds, target, int(block_size))
+
+
+def tv_sums(img: Tensor) -> Tensor:
+    """``tmx::tv_sums`` (``csrc/neighbour_diff.hip``): fp64 ``[B]``, per image of ``img`` ``[B, C, H, W]`` (fp32 / bf16 / fp16, read in place, once)
+    ``Σ|x[i + 1][j] − x[i][j]| + Σ|x[i][j + 1] − x[i][j]|`` over ``C, H, W``: fp32 differences, their absolute values added in fp64, one partial per
+    workgroup, an image's partials added in a fixed order (deterministic).  No host read.  No autograd."""
+    return torch.ops.tmx.tv_sums(img)
+
+
+def image_gradients(img: Tensor) -> Tuple[Tensor, Tensor]:
+    """``tmx::image_gradients`` (``csrc/neighbour_diff.hip``): ``(dy, dx)`` in the dtype and shape of ``img`` ``[B, C, H, W]`` (fp32 / bf16 / fp16, read in
+    place, once): ``dy[i][j] = x[i + 1][j] − x[i][j]`` and ``dx[i][j] = x[i][j + 1] − x[i][j]``, one fp32 subtraction rounded once to the dtype (the bits of
+    the composition); the last row of ``dy`` and the last column of ``dx`` are stored as zeros by the same kernel.  No autograd."""
+    dy, dx = torch.ops.tmx.image_gradients(img)
+    return dy, dx
+
+
+def gradient_tile() -> Tuple[int, int]:
+    """``(fp32 columns per workgroup of the neighbour-difference kernels, rows per strip)``; 16-bit inputs take twice the columns."""
+    columns, rows = torch.ops.tmx.gradient_tile()
+    return int(columns), int(rows)
