@@ -1,10 +1,71 @@
-"""Thin wrappers of the signal-pair ops of ``csrc/signal_pairs.hip`` (SNR, SI-SDR, SA-SDR and the PIT pair matrix)."""
-from typing import Tuple
+"""Thin wrappers of the signal-pair ops of ``csrc/signal_pairs.hip`` (SNR, SI-SDR, SA-SDR and the PIT pair matrix) and of the
+STOI / ESTOI ops of ``csrc/stoi.hip``."""
+import math
+from typing import Dict, Tuple
 
 import torch
 from torch import Tensor
 
 PAIR_DIAGONAL, PAIR_ALL, PAIR_AGGREGATED = 0, 1, 2
+
+_STOI_FS = 10000
+_stoi_table_cache: Dict[torch.device, Tensor] = {}
+_stoi_filter_cache: Dict[Tuple[int, torch.device], Tuple[Tensor, int, int, int]] = {}
+
+
+def _stoi_tables(device: torch.device) -> Tensor:
+    """Hann window ``np.hanning(258)[1:-1]``, then ``cos`` and ``sin`` of ``2 pi i / 512``: 1280 fp64 values, uploaded once per device."""
+    tab = _stoi_table_cache.get(device)
+    if tab is None:
+        k = torch.arange(1, 257, dtype=torch.float64)
+        a = 2 * math.pi * torch.arange(512, dtype=torch.float64) / 512
+        tab = torch.cat([0.5 - 0.5 * torch.cos(2 * math.pi * k / 257), torch.cos(a), torch.sin(a)]).to(device)
+        _stoi_table_cache[device] = tab
+    return tab
+
+
+def _stoi_filter(fs: int, device: torch.device) -> Tuple[Tensor, int, int, int]:
+    """``(h', up, down, n_pre_remove)`` of ``_resample_poly`` for ``fs -> 10 kHz``: the Octave filter scaled by ``up`` and padded in
+    front, uploaded once per ``(fs, device)``.  The trailing padding of ``_resample_poly`` is zeros only: the kernel reads a tap past
+    the end as 0, so the filter does not depend on the signal length."""
+    key = (int(fs), device)
+    hit = _stoi_filter_cache.get(key)
+    if hit is None:
+        g = math.gcd(_STOI_FS, int(fs))
+        up, down = _STOI_FS // g, int(fs) // g
+        if up == down:
+            hit = (torch.empty(0, dtype=torch.float64, device=device), 1, 1, 0)
+        else:
+            from torchmetrics_forked_amd.functional.audio.stoi import _octave_filter
+
+            h = torch.tensor(_octave_filter(_STOI_FS, int(fs)), dtype=torch.float64) * up
+            half_len = (h.numel() - 1) // 2
+            n_pre_pad = down - half_len % down
+            hit = (torch.nn.functional.pad(h, (n_pre_pad, 0)).to(device), up, down, (half_len + n_pre_pad) // down)
+        _stoi_filter_cache[key] = hit
+    return hit
+
+
+def stoi_scores(preds: Tensor, target: Tensor, fs: int, extended: bool) -> Tuple[Tensor, Tensor]:
+    """``tmx::stoi_scores``: STOI (or ESTOI) of every signal of ``preds`` / ``target`` ``[B, T]`` (fp32 / fp64 / bf16 / fp16, read in
+    place; ``target`` is the clean signal) sampled at ``fs``: ``(scores fp64 [B], frames int32 [B])``, ``frames`` the number of STFT frames
+    left after the silent frames are removed; a signal with fewer than 30 scores exactly ``1e-5``.  fp64 on the up-cast samples, the
+    stages of ``functional/audio/stoi.py``; no host read, no atomics (two runs are bit-equal).  No autograd."""
+    filt, up, down, pre = _stoi_filter(fs, preds.device)
+    return torch.ops.tmx.stoi_scores(preds, target, _stoi_tables(preds.device), filt, up, down, pre, bool(extended))
+
+
+def stoi_bands(preds: Tensor, target: Tensor, fs: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """``tmx::stoi_bands``: the third-octave envelopes ``stoi_scores`` correlates, ``(x_tob, y_tob, frames)``: fp64 ``[B, 15, Jmax]`` of the
+    clean and the processed signal (zero past ``frames[b]``) and int32 ``[B]``.  For tests: a window or band gain cancels out of the score."""
+    filt, up, down, pre = _stoi_filter(fs, preds.device)
+    return torch.ops.tmx.stoi_bands(preds, target, _stoi_tables(preds.device), filt, up, down, pre)
+
+
+def stoi_tile() -> Tuple[int, int, int, int, int]:
+    """``(STFT frames per workgroup of the band kernel, segments per workgroup of the segment kernel, outputs per workgroup of the
+    resampler, frames per strip of the kept-frame scan, frames per workgroup of the energy kernel)``."""
+    return tuple(int(v) for v in torch.ops.tmx.stoi_tile())  # type: ignore[return-value]
 
 
 def signal_pair_ratios(preds: Tensor, target: Tensor, scale_invariant: bool, zero_mean: bool, pairing: int, eps: float) -> Tensor:
