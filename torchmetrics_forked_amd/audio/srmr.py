@@ -1,4 +1,5 @@
-"""SpeechReverberationModulationEnergyRatio module (API parity: reference ``audio/srmr.py``); native filterbanks."""
+"""SpeechReverberationModulationEnergyRatio module (API parity: reference ``audio/srmr.py``); native filterbanks.  ``update`` on GPU float
+tensors takes the ``tmx::srmr_*`` kernels of ``csrc/srmr.hip`` without a host read (see ``functional/audio/srmr.py`` for the routes)."""
 from typing import Any, Optional
 
 from torch import Tensor

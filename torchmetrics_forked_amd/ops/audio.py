@@ -1,7 +1,7 @@
-"""Thin wrappers of the signal-pair ops of ``csrc/signal_pairs.hip`` (SNR, SI-SDR, SA-SDR and the PIT pair matrix) and of the
-STOI / ESTOI ops of ``csrc/stoi.hip``."""
+"""Thin wrappers of the signal-pair ops of ``csrc/signal_pairs.hip`` (SNR, SI-SDR, SA-SDR and the PIT pair matrix), of the
+STOI / ESTOI ops of ``csrc/stoi.hip`` and of the SRMR ops of ``csrc/srmr.hip``."""
 import math
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -66,6 +66,115 @@ def stoi_tile() -> Tuple[int, int, int, int, int]:
     """``(STFT frames per workgroup of the band kernel, segments per workgroup of the segment kernel, outputs per workgroup of the
     resampler, frames per strip of the kept-frame scan, frames per workgroup of the energy kernel)``."""
     return tuple(int(v) for v in torch.ops.tmx.stoi_tile())  # type: ignore[return-value]
+
+
+class SrmrTables(NamedTuple):
+    """What the SRMR ops read besides the signal, on one device: ``coefs [N, 10]`` (``_make_erb_filters``), ``mod [8, 2, 3]``
+    (``_compute_modulation_filterbank_and_cutoffs``), the periodic Hamming ``window [w_length]``, ``kstar [N]`` int32 (``None`` when some
+    bandwidth falls below every cutoff ``_cal_srmr_score`` accepts), ``w_length`` and ``w_inc``."""
+
+    coefs: Tensor
+    mod: Tensor
+    window: Tensor
+    kstar: Optional[Tensor]
+    w_length: int
+    w_inc: int
+
+
+_srmr_table_cache: Dict[Tuple[int, int, float, float, float, torch.device], SrmrTables] = {}
+_srmr_hilbert_cache: Dict[Tuple[int, torch.device], Tensor] = {}
+
+
+def srmr_kstar(erbs: Tensor, cutoffs: Tensor) -> Optional[Tuple[int, ...]]:
+    """``k*`` of ``_cal_srmr_score`` for every bandwidth of ``erbs`` (fp64, host), with its comparisons on the same fp64 values;
+    ``None`` where it would raise.  The bandwidth of a signal can only be one of these, so the choice is made ahead of the kernel."""
+    out = []
+    for bw in erbs:
+        if (cutoffs[4] <= bw) and (cutoffs[5] > bw):
+            out.append(5)
+        elif (cutoffs[5] <= bw) and (cutoffs[6] > bw):
+            out.append(6)
+        elif (cutoffs[6] <= bw) and (cutoffs[7] > bw):
+            out.append(7)
+        elif cutoffs[7] <= bw:
+            out.append(8)
+        else:
+            return None
+    return tuple(out)
+
+
+def srmr_tables(fs: int, n_cochlear_filters: int, low_freq: float, min_cf: float, max_cf: float, device: torch.device) -> SrmrTables:
+    """The tables of one argument set, designed on the host in fp64 and uploaded once per
+    ``(fs, n_cochlear_filters, low_freq, min_cf, max_cf, device)``: a second call with the same arguments uploads nothing."""
+    key = (int(fs), int(n_cochlear_filters), float(low_freq), float(min_cf), float(max_cf), device)
+    hit = _srmr_table_cache.get(key)
+    if hit is None:
+        from torchmetrics_forked_amd.functional.audio import srmr
+
+        cpu = torch.device("cpu")
+        w_length, w_inc = math.ceil(0.256 * fs), math.ceil(0.064 * fs)
+        coefs = srmr._make_erb_filters(fs, n_cochlear_filters, low_freq, device=cpu)
+        _, mod, cutoffs, _ = srmr._compute_modulation_filterbank_and_cutoffs(min_cf, max_cf, n=8, fs=fs, q=2, device=cpu)
+        erbs = torch.flipud(srmr._calc_erbs(low_freq, fs, n_cochlear_filters, device=cpu))
+        ks = srmr_kstar(erbs, cutoffs)
+        window = torch.hamming_window(w_length + 1, dtype=torch.float64)[:-1]
+        hit = SrmrTables(coefs.contiguous().to(device), mod.contiguous().to(device), window.contiguous().to(device),
+                         None if ks is None else torch.tensor(ks, dtype=torch.int32).to(device), w_length, w_inc)
+        if len(_srmr_table_cache) >= 64:
+            _srmr_table_cache.clear()
+        _srmr_table_cache[key] = hit
+    return hit
+
+
+def srmr_hilbert_weights(nfft: int, device: torch.device) -> Tensor:
+    """The one-sided weights of ``_hilbert`` (1 at DC and Nyquist, 2 between, 0 above), fp64 ``[nfft]``, uploaded once per length and device."""
+    key = (int(nfft), device)
+    h = _srmr_hilbert_cache.get(key)
+    if h is None:
+        h = torch.zeros(nfft, dtype=torch.float64)
+        if nfft % 2 == 0:
+            h[0] = h[nfft // 2] = 1
+            h[1 : nfft // 2] = 2
+        else:
+            h[0] = 1
+            h[1 : (nfft + 1) // 2] = 2
+        h = h.to(device)
+        if len(_srmr_hilbert_cache) >= 16:
+            _srmr_hilbert_cache.clear()
+        _srmr_hilbert_cache[key] = h
+    return h
+
+
+def srmr_gammatone(preds: Tensor, coefs: Tensor, nfft: int) -> Tensor:
+    """``tmx::srmr_gammatone``: the 4-stage gammatone cascade of ``_erb_filterbank`` on ``preds`` ``[B, T]`` (fp32 / fp64 / bf16 / fp16, read in
+    place with its row stride, up-cast per sample) with the ``[N, 10]`` fp64 table ``coefs``: fp64 ``[B, N, nfft]``, ``nfft >= T``, zeros from
+    ``T`` on.  Per channel four direct-form-I biquads in ``tmx::iir_filter``'s operation order, each stage clamped to ``[-1, 1]`` before it
+    feeds the next (the recursion itself runs on the unclamped values, as ``lfilter``), then the division by the gain.  One thread per
+    (signal, channel); no host read, no atomics (two runs are bit-equal, a signal alone has its bits in a batch).  No autograd."""
+    return torch.ops.tmx.srmr_gammatone(preds, coefs, int(nfft))
+
+
+def srmr_energies(analytic: Tensor, time: int, mod: Tensor, window: Tensor, w_inc: int) -> Tensor:
+    """``tmx::srmr_energies``: modulation-band frame energies of the analytic signal ``[B, N, nfft]`` complex128 (read in place with its row
+    stride; only the first ``time`` samples are used): ``|z|`` through the ``M`` biquads of ``mod`` ``[M, 2, 3]`` (no clamp), then
+    ``Σ_n (y[n] window[n − f w_inc])²`` over the ``F = 1 + (time − w_length) // w_inc`` frames, samples in order: fp64 ``[B, N, M, F]``.
+    Needs ``w_length <= 4 w_inc`` (true of SRMR's 256 ms / 64 ms at every rate).  Neither the ``[B, N, M, time]`` filter output nor a frame
+    tensor is allocated.  No host read, no atomics.  No autograd."""
+    return torch.ops.tmx.srmr_energies(analytic, int(time), mod, window, int(w_inc))
+
+
+def srmr_scores(energy: Tensor, kstar: Tensor, norm: bool) -> Tensor:
+    """``tmx::srmr_scores``: SRMR of every signal from its energies ``[B, N, M, F]`` fp64: the optional 30 dB normalisation (``norm``), the
+    frame means, the cumulative energy percentage from the lowest channel (index ``N − 1``) upwards, ``k90`` = the first count above 90,
+    ``k* = kstar[k90]`` (int32 ``[N]``, see ``srmr_kstar``) and ``Σ avg[:, :4] / Σ avg[:, 4:k*]``: fp64 ``[B]``.  A signal without a ``k90``
+    (silent, NaN) scores NaN and leaves the others as they are.  No host read, no atomics.  No autograd."""
+    return torch.ops.tmx.srmr_scores(energy, kstar, bool(norm))
+
+
+def srmr_tile() -> Tuple[int, int, int]:
+    """``(time steps per staged block and threads per workgroup of the two filter kernels, frames that can hold one sample, bytes up to
+    which the zero-filled window is kept in LDS)``."""
+    return tuple(int(v) for v in torch.ops.tmx.srmr_tile())  # type: ignore[return-value]
 
 
 def signal_pair_ratios(preds: Tensor, target: Tensor, scale_invariant: bool, zero_mean: bool, pairing: int, eps: float) -> Tensor:
