@@ -1,5 +1,5 @@
 """Thin wrappers of the signal-pair ops of ``csrc/signal_pairs.hip`` (SNR, SI-SDR, SA-SDR and the PIT pair matrix), of the
-STOI / ESTOI ops of ``csrc/stoi.hip`` and of the SRMR ops of ``csrc/srmr.hip``."""
+STOI / ESTOI ops of ``csrc/stoi.hip``, of the SRMR ops of ``csrc/srmr.hip`` and of the SDR ops of ``csrc/sdr.hip``."""
 import math
 from typing import Dict, NamedTuple, Optional, Tuple
 
@@ -175,6 +175,41 @@ def srmr_tile() -> Tuple[int, int, int]:
     """``(time steps per staged block and threads per workgroup of the two filter kernels, frames that can hold one sample, bytes up to
     which the zero-filled window is kept in LDS)``."""
     return tuple(int(v) for v in torch.ops.tmx.srmr_tile())  # type: ignore[return-value]
+
+
+def sdr_scores(preds: Tensor, target: Tensor, filter_length: int, zero_mean: bool, load_diag: Optional[float], pairing: int) -> Tensor:
+    """``tmx::sdr_scores``: fp64 ``signal_distortion_ratio`` in dB of ``preds`` / ``target`` ``[G, S, T]`` (fp32 / bf16 / fp16 of one dtype, made
+    contiguous and read in place).  In fp64 on the up-cast samples: the means are subtracted on load when ``zero_mean``; the first
+    ``filter_length`` lags of the target's autocorrelation and of the cross-correlation are summed directly (no FFT; on
+    ``v_mfma_f64_16x16x4_f64`` for signals of 16 384 samples or more whose filter fills its 256-lag tiles, else on the vector ALU); the composition's
+    normalisation ``1 / max(‖·‖, 1e-6)`` is applied to the sums; ``load_diag`` is added to lag 0; the symmetric Toeplitz system is solved
+    by the Levinson recursion in LDS; ``10 log10(coh / (1 − coh))`` with ``coh = Σ b x``.  ``pairing`` ``PAIR_DIAGONAL``: ``[G, S]``, the pairs
+    ``(p_s, t_s)``; ``PAIR_ALL``: ``[G, S, S]`` with ``out[g, j, i] = SDR(preds[g, i], target[g, j])``, every target's autocorrelation and Durbin
+    vector computed once.  ``1 <= filter_length <= sdr_tile()[3]``.  A silent or NaN target scores NaN.  No full-size temporary, no
+    host read, no atomics (two runs are bit-equal).  No autograd."""
+    return torch.ops.tmx.sdr_scores(preds, target, int(filter_length), bool(zero_mean), None if load_diag is None else float(load_diag), int(pairing))
+
+
+def sdr_correlations(preds: Tensor, target: Tensor, filter_length: int, zero_mean: bool, pairing: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """``tmx::sdr_correlations``: the raw fp64 lag sums ``sdr_scores`` starts from, before any scaling: ``r[g, j, k] = Σ_n t~_j[n] t~_j[n + k]``
+    ``[G, S, L]``; ``c = Σ_n t~_j[n] p~_i[n + k]`` as ``[G, S, L]`` (``PAIR_DIAGONAL``, ``i = j``) or ``[G, S(target), S(preds), L]`` (``PAIR_ALL``);
+    ``pp[g, i] = Σ p~_i²`` ``[G, S]``.  For tests: on integer-valued signals every one of them is exact."""
+    r, c, pp = torch.ops.tmx.sdr_correlations(preds, target, int(filter_length), bool(zero_mean), int(pairing))
+    return r, c, pp
+
+
+def sdr_chunks(g: int, s: int, t: int, filter_length: int, pairing: int) -> int:
+    """How many chunks the correlation pass of ``sdr_scores`` splits every signal of a ``[g, s, t]`` call into: a function of the shape,
+    the filter length and the pairing alone, unless ``TMX_SDR_CHUNK`` (samples per chunk, read per call) overrides it.  Only the last
+    chunk may be short."""
+    return int(torch.ops.tmx.sdr_chunks(int(g), int(s), int(t), int(filter_length), int(pairing)))
+
+
+def sdr_tile() -> Tuple[int, int, int, int, int, int, int, int]:
+    """``(lags per workgroup of the VALU form of the correlation pass, adjacent lags per lane, samples staged in LDS at a time, the largest
+    filter_length (3 L fp64 values in LDS), the longest filter the solve runs in a single wave, right-hand sides one recursion serves
+    at most, lags per workgroup of the matrix-core form, the signal length from which that form is used)``."""
+    return tuple(int(v) for v in torch.ops.tmx.sdr_tile())  # type: ignore[return-value]
 
 
 def signal_pair_ratios(preds: Tensor, target: Tensor, scale_invariant: bool, zero_mean: bool, pairing: int, eps: float) -> Tensor:
