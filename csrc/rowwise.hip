@@ -5,8 +5,10 @@
 //                      functional/classification/stat_scores.py:363-393 (select_topk one-hot, compare, sum).  The
 //                      k best entries are found by k wave arg-max rounds over the register-resident row, each round
 //                      restricted to entries ordered after the previous pick — (value desc, index asc), NaN first
-//                      as torch.topk orders it — so no exclusion state is kept.  Per row: tp / fn on the target
-//                      class, fp on every other pick; tn is derived on the host from the valid-row count.
+//                      as torch.topk orders it — so no exclusion state is kept.  Lane ``round % 64`` records the pick
+//                      and the wave counts its 64 recorded picks every 64 rounds, so any k <= C <= 2048 is served.
+//                      Per row: tp / fn on the target class, fp on every other pick; tn is derived on the host from
+//                      the valid-row count.
 //   mc_hinge     (K11) multiclass hinge loss (crammer-singer or one-vs-all) with the batch's softmax decision read
 //                      from the device range flag; every intermediate rounded to the input dtype, as the reference's
 //                      tensor expression computes it (functional/classification/hinge.py:118-140).
@@ -53,7 +55,14 @@ __global__ __launch_bounds__(kRowBlock) void topk_stats_kernel(const T* __restri
   for (int64_t r = (int64_t)blockIdx.x * (kRowBlock / kWave) + threadIdx.x / kWave; r < M; r += waves) {
     const int64_t t = target[r];
     if ((has_ignore && t == ignore_index) || t < 0 || t >= C) continue;  // wave-uniform
-    int sel = -1;  // lane j < k holds the j-th pick
+    const int64_t base = samplewise ? (r / X) * C : 0;
+    bool hit = false;
+    int sel = -1;  // lane j holds pick j, 64 picks at a time
+    // the recorded picks: the target among them is the row's tp, every other one an fp of its class
+    auto flush = [&]() {
+      hit |= __ballot(sel >= 0 && sel == t) != 0;
+      if (sel >= 0 && sel != t) atomic_add_i64(fp + base + sel, 1);
+    };
     if (labels != nullptr) {
       const int64_t p = labels[r];
       sel = (lane == 0 && p >= 0 && p < C) ? static_cast<int>(p) : -1;
@@ -71,14 +80,16 @@ __global__ __launch_bounds__(kRowBlock) void topk_stats_kernel(const T* __restri
           if (c < C && (round == 0 || before(pv, pi, v[j], c)) && before(v[j], c, bv, bi)) { bv = v[j]; bi = c; }
         }
         wave_argmax(bv, bi);
-        if (lane == round) sel = bi;
+        if (lane == (round & (kWave - 1))) sel = bi;
         pv = bv;
         pi = bi;
+        if ((round & (kWave - 1)) == kWave - 1 && round + 1 < k) {  // wave-uniform; never taken for k <= 64
+          flush();
+          sel = -1;
+        }
       }
     }
-    const bool hit = __ballot(sel >= 0 && sel == t) != 0;
-    const int64_t base = samplewise ? (r / X) * C : 0;
-    if (sel >= 0 && sel != t) atomic_add_i64(fp + base + sel, 1);
+    flush();
     if (lane == 0) {
       atomic_add_i64((hit ? tp : fn) + base + t, 1);
       atomic_add_i64(nvalid + (samplewise ? r / X : 0), 1);
@@ -87,8 +98,9 @@ __global__ __launch_bounds__(kRowBlock) void topk_stats_kernel(const T* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------- hinge
-// NaN-propagating max (torch.max semantics)
+// NaN-propagating max / min (torch.max / torch.min semantics)
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a || a > b) ? a : b; }
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || a < b) ? a : b; }
 __device__ __forceinline__ float nan_clamp0(float x) { return (x != x || x > 0.f) ? x : 0.f; }
 
 template <typename T, int VPT, bool OVA>
@@ -205,9 +217,10 @@ __global__ __launch_bounds__(kRowBlock) void ml_ranking_kernel(const T* __restri
       float pm = INFINITY;
 #pragma unroll
       for (int j = 0; j < VPT; ++j)
-        if (lane + j * kWave < L) pm = fminf(pm, rel[j] ? v[j] : round_trip<T>(v[j] + g));
+        if (lane + j * kWave < L) pm = nan_min(pm, rel[j] ? v[j] : round_trip<T>(v[j] + g));
+      // NaN-propagating like the reference's row min: a NaN score or shift (|min| of a batch holding one) counts 0
 #pragma unroll
-      for (int off = 32; off > 0; off >>= 1) pm = fminf(pm, __shfl_xor(pm, off, kWave));
+      for (int off = 32; off > 0; off >>= 1) pm = nan_min(pm, __shfl_xor(pm, off, kWave));
       int cnt = 0;
 #pragma unroll
       for (int j = 0; j < VPT; ++j) cnt += (lane + j * kWave < L) && v[j] >= pm;
@@ -285,7 +298,7 @@ std::vector<at::Tensor> topk_stats(const at::Tensor& preds, const c10::optional<
   TORCH_CHECK(target.is_cuda() && target.scalar_type() == at::kLong && target.is_contiguous(), "topk_stats: target int64");
   const int64_t M = target.numel();
   const int C = static_cast<int>(num_classes);
-  TORCH_CHECK(k >= 1 && k <= C, "topk_stats: k out of range");
+  TORCH_CHECK(k >= 1 && k <= C && k <= 64 * 32, "topk_stats: k out of range (1 <= k <= min(C, 2048))");
   TORCH_CHECK(X >= 1 && M % X == 0, "topk_stats: rows must be a multiple of X");
   const bool use_labels = labels.has_value();
   if (use_labels) {
