@@ -1,5 +1,6 @@
-"""Thin wrappers of the class-overlap ops of ``csrc/segment_overlap.hip`` behind the segmentation metrics (mean IoU, Dice, generalized Dice)."""
-from typing import Tuple
+"""Thin wrappers of the class-overlap ops of ``csrc/segment_overlap.hip`` behind the segmentation metrics (mean IoU, Dice, generalized Dice)
+and of the boundary-distance ops of ``csrc/hausdorff.hip`` behind the Hausdorff distance."""
+from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -7,6 +8,7 @@ from torch import Tensor
 METRIC_IOU, METRIC_DICE, METRIC_GENERALIZED_DICE = 0, 1, 2
 DICE_OPTIONS = {"micro": 0, "macro": 1, "weighted": 2, "none": 3}
 WEIGHT_OPTIONS = {"square": 0, "simple": 1, "linear": 2}
+DISTANCE_METRICS = {"euclidean": 0, "chessboard": 1, "taxicab": 2}
 
 
 def segment_overlap_index(preds: Tensor, target: Tensor, num_classes: int) -> Tensor:
@@ -39,3 +41,30 @@ def segment_overlap_chunks(B: int, n: int, C: int, onehot: bool) -> int:
     """Chunks the overlap kernels split every row of ``n`` pixels into (index form: ``B`` rows; one-hot form: ``B * C``): a function of the
     shape alone, and of ``TMX_SEGMENT_CHUNK`` where a test sets it."""
     return int(torch.ops.tmx.segment_overlap_chunks(int(B), int(n), int(C), bool(onehot)))
+
+
+def _spacing_list(spacing: Optional[Sequence[float]]) -> list:
+    return [] if spacing is None else [float(v) for v in spacing]
+
+
+def hausdorff_index(preds: Tensor, target: Tensor, num_classes: int, include_background: bool, metric: int,
+                    spacing: Optional[Sequence[float]], directed: bool) -> Tensor:
+    """``tmx::hausdorff_index``: fp32 ``[B, C']`` Hausdorff distances between the mask boundaries of every kept class of the label maps
+    ``preds`` / ``target`` ``[B, H, W]`` (uint8 / int16 / int32 / int64, the two may differ, read in place: membership is ``label == class``
+    inside the kernel).  ``metric``: ``DISTANCE_METRICS``; ``spacing``: ``None`` or ``(sy, sx)``; ``directed``: ``h(preds -> target)`` only.
+    An empty source mask gives 0, a non-empty one against an empty mask ``inf``.  ``H`` and ``W`` at most ``hausdorff_tile()[5]`` and
+    ``[4]``.  Integer atomics: two runs are bit-equal.  No host read, no autograd."""
+    return torch.ops.tmx.hausdorff_index(preds, target, int(num_classes), bool(include_background), int(metric), _spacing_list(spacing), bool(directed))
+
+
+def hausdorff_onehot(preds: Tensor, target: Tensor, num_classes: int, include_background: bool, metric: int,
+                     spacing: Optional[Sequence[float]], directed: bool) -> Tensor:
+    """``tmx::hausdorff_onehot``: the same distances from masks ``[B, C, H, W]`` (bool / uint8 / int32 / int64, the two may differ), nonzero
+    meaning member."""
+    return torch.ops.tmx.hausdorff_onehot(preds, target, int(num_classes), bool(include_background), int(metric), _spacing_list(spacing), bool(directed))
+
+
+def hausdorff_tile() -> Tuple[int, int, int, int, int, int]:
+    """``(columns per workgroup of the column kernel, row strips of a column block, rows in flight per lane, rows per workgroup of the row
+    kernel, largest W, largest H)``."""
+    return tuple(int(v) for v in torch.ops.tmx.hausdorff_tile())  # type: ignore[return-value]
