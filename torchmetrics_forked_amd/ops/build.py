@@ -69,9 +69,11 @@ def _common_flags() -> List[str]:
 # per-source extra flags: image.hip's SSIM kernel keeps its MFMA accumulators in VGPRs (the AGPR form read every
 # result back with one v_accvgpr_read per value: ~50 extra VALU instructions per band of its VALU-bound loop)
 # py_columns.cpp is the library's CPython entry point (``ops.py_module()``): Python headers, libtorch_python at link
-# hausdorff.hip's fp32 is one scaled offset per lane: it is compiled without the packed fp32 instructions
+# hausdorff.hip's fp32 is one scaled offset per lane, infolm.hip's one exp / log / pow per element: both are compiled without the packed
+# fp32 instructions
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _EXTRA_FLAGS = {"image.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "py_columns.cpp": [f"-I{sysconfig.get_paths()['include']}"],
-                "hausdorff.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                "hausdorff.hip": _NO_PACKED_FP32, "infolm.hip": _NO_PACKED_FP32}
 
 
 def _flags_for(src: Path) -> List[str]:
