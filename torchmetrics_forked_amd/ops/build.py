@@ -70,10 +70,10 @@ def _common_flags() -> List[str]:
 # result back with one v_accvgpr_read per value: ~50 extra VALU instructions per band of its VALU-bound loop)
 # py_columns.cpp is the library's CPython entry point (``ops.py_module()``): Python headers, libtorch_python at link
 # hausdorff.hip's fp32 is one scaled offset per lane, infolm.hip's one exp / log / pow per element: both are compiled without the packed
-# fp32 instructions
+# fp32 instructions; cluster_scatter.hip converts every element to fp64 at once and is compiled the same way
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _EXTRA_FLAGS = {"image.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "py_columns.cpp": [f"-I{sysconfig.get_paths()['include']}"],
-                "hausdorff.hip": _NO_PACKED_FP32, "infolm.hip": _NO_PACKED_FP32}
+                "hausdorff.hip": _NO_PACKED_FP32, "infolm.hip": _NO_PACKED_FP32, "cluster_scatter.hip": _NO_PACKED_FP32}
 
 
 def _flags_for(src: Path) -> List[str]:
