@@ -246,21 +246,15 @@ int64_t box_batch_chunks(int64_t B, int64_t C, int64_t H, int64_t W) {
 std::tuple<at::Tensor, at::Tensor, at::Tensor> box_rmse_maps(const at::Tensor& preds_in, const at::Tensor& target_in, int64_t window_size,
                                                              int64_t crop, bool with_target_mean) {
   const char* name = "box_rmse_maps";
-  TORCH_CHECK(preds_in.is_cuda() && target_in.is_cuda(), name, ": expected GPU tensors");
-  TORCH_CHECK(preds_in.device() == target_in.device(), name, ": preds and target on different devices");
-  TORCH_CHECK(preds_in.dim() == 4 && preds_in.sizes() == target_in.sizes(), name, ": expected matching [B, C, H, W]");
-  TORCH_CHECK(preds_in.scalar_type() == target_in.scalar_type(), name, ": dtype mismatch");
-  const auto dtype = preds_in.scalar_type();
-  TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16 || dtype == at::kHalf, name, ": unsupported dtype ", dtype);
+  at::Tensor p, t;
+  std::tie(p, t) = checked_pair(preds_in, target_in, 4, "[B, C, H, W]", name);
   TORCH_CHECK(window_size >= 2 && window_size <= 16, name, ": unsupported window size ", window_size);
-  const int64_t B = preds_in.size(0), C = preds_in.size(1), H = preds_in.size(2), W = preds_in.size(3);
+  const int64_t B = p.size(0), C = p.size(1), H = p.size(2), W = p.size(3);
   TORCH_CHECK(B >= 1 && C >= 1, name, ": empty input");
   // crop is the caller's round(window_size / 2); with it above window_size / 2 one reflection per side is enough
   TORCH_CHECK(crop >= window_size / 2 && H > 2 * crop && W > 2 * crop, name, ": the plane must be larger than twice the crop");
   TORCH_CHECK(H * W <= INT32_MAX, name, ": plane too large");
-  const at::DeviceGuard guard(preds_in.device());
-  auto p = preds_in.contiguous();
-  auto t = target_in.contiguous();
+  const at::DeviceGuard guard(p.device());
 
   const int64_t chunks = box_batch_chunks(B, C, H, W);
   const int64_t per_chunk = (B + chunks - 1) / chunks;
@@ -272,7 +266,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> box_rmse_maps(const at::Tensor& p
   auto mean_part = with_target_mean ? at::empty({chunks, C, H, W}, f32) : at::empty({0}, f32);
   auto crop_part = at::empty({C, chunks * strips * col_blocks}, p.options().dtype(at::kDouble));
   const dim3 grid(static_cast<unsigned>(C * chunks), static_cast<unsigned>(col_blocks), static_cast<unsigned>(strips));
-  dispatch_float3(dtype, name, [&](auto tag) {
+  dispatch_float3(p.scalar_type(), name, [&](auto tag) {
     using T = decltype(tag);
     dispatch_box_window(window_size, name, [&](auto ws) {
       auto launch = [&](auto tm) {

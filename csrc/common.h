@@ -10,7 +10,10 @@
 #include <torch/library.h>
 
 #include <cstdint>
+#include <initializer_list>
+#include <tuple>
 #include <type_traits>
+#include <utility>
 
 #include "device_common.h"
 
@@ -66,6 +69,27 @@ void dispatch_float3(at::ScalarType dtype, const char* name, F&& f) {
     case at::kHalf: f(__half{}); break;
     default: TORCH_CHECK(false, name, ": unsupported dtype ", dtype);
   }
+}
+
+// The checks a two-tensor entry point opens with, in this order: both on the GPU, on one device, `rank` dims of one shape (`layout` is
+// the op's own text for it, e.g. "[G, S, T]"), one dtype, and that dtype fp32 / bf16 / fp16.  Returns the contiguous pair.
+// What counts as empty stays with the op: some answer an empty batch with an empty result, some test only the extents they divide by.
+inline std::pair<at::Tensor, at::Tensor> checked_pair(const at::Tensor& preds, const at::Tensor& target, int64_t rank, const char* layout,
+                                                      const char* name) {
+  TORCH_CHECK(preds.is_cuda() && target.is_cuda(), name, ": expected GPU tensors");
+  TORCH_CHECK(preds.device() == target.device(), name, ": preds and target on different devices");
+  TORCH_CHECK(preds.dim() == rank && preds.sizes() == target.sizes(), name, ": expected matching ", layout);
+  TORCH_CHECK(preds.scalar_type() == target.scalar_type(), name, ": dtype mismatch");
+  const auto dtype = preds.scalar_type();
+  TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16 || dtype == at::kHalf, name, ": unsupported dtype ", dtype);
+  return {preds.contiguous(), target.contiguous()};
+}
+
+// True when rows of `extent` elements can be walked by 16-byte loads or stores from every one of `ptrs`.
+inline bool vec16_ok(int64_t extent, size_t element_size, std::initializer_list<const void*> ptrs) {
+  for (const void* ptr : ptrs)
+    if (reinterpret_cast<uintptr_t>(ptr) & 15) return false;
+  return extent % (16 / static_cast<int64_t>(element_size)) == 0;
 }
 
 }  // namespace tmx

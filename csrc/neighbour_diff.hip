@@ -373,7 +373,7 @@ NdInputs nd_inputs(const at::Tensor& x_in, const char* name) {
   in.cblocks = (in.W + kWave * V - 1) / (kWave * V);
   TORCH_CHECK(in.B * in.C <= INT32_MAX / (in.strips * in.cblocks), name, ": too many workgroups for one launch");
   in.groups = in.B * in.C * in.strips * in.cblocks;
-  in.vec = !nd_vec_off() && in.W % V == 0 && (reinterpret_cast<uintptr_t>(in.x.data_ptr()) & 15) == 0;
+  in.vec = !nd_vec_off() && vec16_ok(in.W, in.x.element_size(), {in.x.data_ptr()});
   return in;
 }
 

@@ -524,16 +524,13 @@ SdrGeometry sdr_geometry(int64_t G, int64_t S, int64_t T, int64_t L, int64_t pai
   return geo;
 }
 
-void sdr_check(const at::Tensor& preds, const at::Tensor& target, int64_t L, int64_t pairing, const char* name) {
-  TORCH_CHECK(preds.is_cuda() && target.is_cuda(), name, ": expected GPU tensors");
-  TORCH_CHECK(preds.device() == target.device(), name, ": preds and target on different devices");
-  TORCH_CHECK(preds.dim() == 3 && preds.sizes() == target.sizes(), name, ": expected matching [G, S, T]");
-  TORCH_CHECK(preds.scalar_type() == target.scalar_type(), name, ": dtype mismatch");
-  const auto dtype = preds.scalar_type();
-  TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16 || dtype == at::kHalf, name, ": unsupported dtype ", dtype);
+// the contiguous pair of a checked call
+std::pair<at::Tensor, at::Tensor> sdr_check(const at::Tensor& preds, const at::Tensor& target, int64_t L, int64_t pairing, const char* name) {
+  auto pair = checked_pair(preds, target, 3, "[G, S, T]", name);
   TORCH_CHECK(preds.numel() > 0, name, ": empty input");
   TORCH_CHECK(L >= 1 && L <= kSdrMaxL, name, ": filter_length must be in [1, ", kSdrMaxL, "]");
   TORCH_CHECK(pairing == 0 || pairing == 1, name, ": pairing must be 0 (diagonal) or 1 (all pairs)");
+  return pair;
 }
 
 // The form of pass C, from the filter and the signal length alone (what a diagonal call and a pair-matrix call on the same signals
@@ -550,11 +547,9 @@ unsigned sdr_grid(int64_t n, const char* name) {
 }
 
 // the folded lag sums rc [G S Q][L + 1]: row (g, j, q), slots 0 .. L − 1 the lags and slot L = Σ x~² of the series
-at::Tensor sdr_lag_sums(const at::Tensor& preds_in, const at::Tensor& target_in, int64_t L, bool zero_mean, int64_t pairing, const SdrGeometry& geo,
+at::Tensor sdr_lag_sums(const at::Tensor& p, const at::Tensor& t, int64_t L, bool zero_mean, int64_t pairing, const SdrGeometry& geo,
                         const char* name) {
-  const int64_t G = preds_in.size(0), S = preds_in.size(1), T = preds_in.size(2), nsig = G * S;
-  auto p = preds_in.contiguous();
-  auto t = target_in.contiguous();
+  const int64_t G = p.size(0), S = p.size(1), T = p.size(2), nsig = G * S;
   const auto f64 = p.options().dtype(at::kDouble);
   const int64_t rows = nsig * geo.Q, slots = L + 1;
   const int64_t q_tiles = (geo.Q + kSdrSeriesTile - 1) / kSdrSeriesTile;
@@ -646,11 +641,11 @@ int64_t sdr_chunks(int64_t G, int64_t S, int64_t T, int64_t L, int64_t pairing) 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> sdr_correlations(const at::Tensor& preds, const at::Tensor& target, int64_t L, bool zero_mean,
                                                                 int64_t pairing) {
   const char* name = "sdr_correlations";
-  sdr_check(preds, target, L, pairing, name);
+  const auto in = sdr_check(preds, target, L, pairing, name);
   const at::DeviceGuard guard(preds.device());
   const int64_t G = preds.size(0), S = preds.size(1), T = preds.size(2);
   const SdrGeometry geo = sdr_geometry(G, S, T, L, pairing);
-  auto rc = sdr_lag_sums(preds, target, L, zero_mean, pairing, geo, name).view({G, S, geo.Q, L + 1});
+  auto rc = sdr_lag_sums(in.first, in.second, L, zero_mean, pairing, geo, name).view({G, S, geo.Q, L + 1});
   auto r = rc.select(2, 0).narrow(2, 0, L).contiguous();
   if (pairing == 1) return {r, rc.narrow(2, 1, S).narrow(3, 0, L).contiguous(), rc.select(1, 0).narrow(1, 1, S).select(2, L).contiguous()};
   return {r, rc.select(2, 1).narrow(2, 0, L).contiguous(), rc.select(2, 1).select(2, L).contiguous()};
@@ -660,11 +655,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> sdr_correlations(const at::Tensor
 // out[g, j, i] = SDR(preds[g, i], target[g, j]).
 at::Tensor sdr_scores(const at::Tensor& preds, const at::Tensor& target, int64_t L, bool zero_mean, c10::optional<double> load_diag, int64_t pairing) {
   const char* name = "sdr_scores";
-  sdr_check(preds, target, L, pairing, name);
+  const auto in = sdr_check(preds, target, L, pairing, name);
   const at::DeviceGuard guard(preds.device());
   const int64_t G = preds.size(0), S = preds.size(1), T = preds.size(2);
   const SdrGeometry geo = sdr_geometry(G, S, T, L, pairing);
-  auto rc = sdr_lag_sums(preds, target, L, zero_mean, pairing, geo, name);
+  auto rc = sdr_lag_sums(in.first, in.second, L, zero_mean, pairing, geo, name);
   const auto f64 = rc.options();
   at::Tensor out = pairing == 1 ? at::empty({G, S, S}, f64) : at::empty({G, S}, f64);
   const int64_t npred = pairing == 1 ? S : 1;

@@ -353,20 +353,13 @@ int64_t signal_chunks(int64_t G, int64_t S, int64_t T, int64_t pairing) {
 at::Tensor signal_pair_ratios(const at::Tensor& preds_in, const at::Tensor& target_in, bool scale_invariant, bool zero_mean, int64_t pairing,
                               double eps) {
   const char* name = "signal_pair_ratios";
-  TORCH_CHECK(preds_in.is_cuda() && target_in.is_cuda(), name, ": expected GPU tensors");
-  TORCH_CHECK(preds_in.device() == target_in.device(), name, ": preds and target on different devices");
-  TORCH_CHECK(preds_in.dim() == 3 && preds_in.sizes() == target_in.sizes(), name, ": expected matching [G, S, T]");
-  TORCH_CHECK(preds_in.scalar_type() == target_in.scalar_type(), name, ": dtype mismatch");
-  const auto dtype = preds_in.scalar_type();
-  TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16 || dtype == at::kHalf, name, ": unsupported dtype ", dtype);
-  TORCH_CHECK(preds_in.numel() > 0, name, ": empty input");
+  at::Tensor p, t;
+  std::tie(p, t) = checked_pair(preds_in, target_in, 3, "[G, S, T]", name);
+  TORCH_CHECK(p.numel() > 0, name, ": empty input");
   TORCH_CHECK(pairing >= 0 && pairing <= 2, name, ": pairing must be 0, 1 or 2");
-  const at::DeviceGuard guard(preds_in.device());
-  const int64_t G = preds_in.size(0), S = preds_in.size(1), T = preds_in.size(2);
-  auto p = preds_in.contiguous();
-  auto t = target_in.contiguous();
-  const int64_t V = 16 / static_cast<int64_t>(p.element_size());
-  const bool vec = T % V == 0 && (reinterpret_cast<uintptr_t>(p.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
+  const at::DeviceGuard guard(p.device());
+  const int64_t G = p.size(0), S = p.size(1), T = p.size(2);
+  const bool vec = vec16_ok(T, p.element_size(), {p.data_ptr(), t.data_ptr()});
 
   const SigGeometry geo = signal_geometry(G, S, pairing);
   const int64_t nsig = G * S;
@@ -389,7 +382,7 @@ at::Tensor signal_pair_ratios(const at::Tensor& preds_in, const at::Tensor& targ
   SigFold f{part.data_ptr<double>(), nwg, S, geo.tiles, chunks, nsig, geo.E, static_cast<int>(pairing), !scale_invariant, eps,
             static_cast<double>(T), mean, alpha, tt, out.data_ptr<double>()};
 
-  dispatch_float3(dtype, name, [&](auto tag) {
+  dispatch_float3(p.scalar_type(), name, [&](auto tag) {
     using T_ = decltype(tag);
     if (zero_mean) {
       SigArgs am = a;

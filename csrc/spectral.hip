@@ -251,20 +251,11 @@ bool spectral_vec_off() {
 }
 
 SpectralInputs spectral_inputs(const at::Tensor& preds_in, const at::Tensor& target_in, int64_t min_bands, const char* name) {
-  TORCH_CHECK(preds_in.is_cuda() && target_in.is_cuda(), name, ": expected GPU tensors");
-  TORCH_CHECK(preds_in.device() == target_in.device(), name, ": preds and target on different devices");
-  TORCH_CHECK(preds_in.dim() == 4 && preds_in.sizes() == target_in.sizes(), name, ": expected matching [B, C, H, W]");
-  TORCH_CHECK(preds_in.scalar_type() == target_in.scalar_type(), name, ": dtype mismatch");
-  const auto dtype = preds_in.scalar_type();
-  TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16 || dtype == at::kHalf, name, ": unsupported dtype ", dtype);
-  const int64_t B = preds_in.size(0), C = preds_in.size(1), HW = preds_in.size(2) * preds_in.size(3);
+  const auto [p, t] = checked_pair(preds_in, target_in, 4, "[B, C, H, W]", name);
+  const int64_t B = p.size(0), C = p.size(1), HW = p.size(2) * p.size(3);
   TORCH_CHECK(B >= 1 && HW >= 1, name, ": empty input");
   TORCH_CHECK(C >= min_bands && C <= INT32_MAX, name, ": expected at least ", min_bands, " bands");
-  auto p = preds_in.contiguous();
-  auto t = target_in.contiguous();
-  const int64_t V = 16 / static_cast<int64_t>(p.element_size());
-  const bool vec = !spectral_vec_off() && HW % V == 0 && (reinterpret_cast<uintptr_t>(p.data_ptr()) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
+  const bool vec = !spectral_vec_off() && vec16_ok(HW, p.element_size(), {p.data_ptr(), t.data_ptr()});
   return {p, t, B, C, HW, vec};
 }
 

@@ -279,8 +279,7 @@ at::Tensor uqi_run(const at::Tensor& a, const at::Tensor& b, int64_t pairs, int6
   auto partial = at::empty({pairs, strips * col_blocks}, a.options().dtype(at::kDouble));
   const dim3 grid(static_cast<unsigned>(pairs), static_cast<unsigned>(col_blocks), static_cast<unsigned>(strips));
   static const bool v2_off = std::getenv("TMX_UQI_V1") != nullptr;  // A/B knob (tools/uqi_bench.py)
-  const bool v2 = !v2_off && a.scalar_type() == at::kFloat && W % 4 == 0 && (reinterpret_cast<uintptr_t>(a.data_ptr()) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(b.data_ptr()) & 15) == 0;
+  const bool v2 = !v2_off && a.scalar_type() == at::kFloat && vec16_ok(W, sizeof(float), {a.data_ptr(), b.data_ptr()});
   if (v2) {
     dispatch_odd_window(KS, name, [&](auto ks) {
       hipLaunchKernelGGL((uqi_pair_v2_kernel<decltype(ks)::value, BAND>), grid, dim3(kUqiThreads), 0, stream(), a.data_ptr<float>(),
@@ -307,16 +306,9 @@ at::Tensor uqi_run(const at::Tensor& a, const at::Tensor& b, int64_t pairs, int6
 // preds / target [P, H, W] planes, fp32 / bf16 / fp16; wy / wx fp32 [KS] windows of the H / W axis, KS odd in 3 .. 15.
 // Returns fp64 [P]: per plane the sum of the UQI over all valid windows.
 at::Tensor uqi_sums(const at::Tensor& preds_in, const at::Tensor& target_in, const at::Tensor& wy_in, const at::Tensor& wx_in, double eps) {
-  TORCH_CHECK(preds_in.is_cuda() && target_in.is_cuda(), "uqi_sums: expected GPU tensors");
-  TORCH_CHECK(preds_in.device() == target_in.device(), "uqi_sums: preds and target on different devices");
-  TORCH_CHECK(preds_in.dim() == 3 && preds_in.sizes() == target_in.sizes(), "uqi_sums: expected matching [P, H, W]");
-  TORCH_CHECK(preds_in.scalar_type() == target_in.scalar_type(), "uqi_sums: dtype mismatch");
-  const auto dtype = preds_in.scalar_type();
-  TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16 || dtype == at::kHalf, "uqi_sums: unsupported dtype ", dtype);
-  const auto win = uqi_windows(preds_in, wy_in, wx_in, "uqi_sums");
-  const at::DeviceGuard guard(preds_in.device());
-  auto p = preds_in.contiguous();
-  auto t = target_in.contiguous();
+  const auto [p, t] = checked_pair(preds_in, target_in, 3, "[P, H, W]", "uqi_sums");
+  const auto win = uqi_windows(p, wy_in, wx_in, "uqi_sums");
+  const at::DeviceGuard guard(p.device());
   const int64_t P = p.size(0), H = p.size(1), W = p.size(2);
   if (P == 0) return at::zeros({0}, p.options().dtype(at::kDouble));
   return uqi_run<false>(p, t, P, H, W, 0, 1, win, eps, "uqi_sums");

@@ -273,19 +273,13 @@ void vif_run(const at::Tensor& p, const at::Tensor& t, float sigma_n_sq, const i
 // preds / target [P, H, W] planes (P = B*C), fp32 / bf16 / fp16, H, W >= 41.  Returns fp64 [4, 2, P]: per scale and plane
 // the sums over all valid windows of log10(1 + g² st² / (sv² + sn²)) and of log10(1 + st² / sn²).
 at::Tensor vif_sums(const at::Tensor& preds_in, const at::Tensor& target_in, double sigma_n_sq) {
-  TORCH_CHECK(preds_in.is_cuda() && target_in.is_cuda(), "vif_sums: expected GPU tensors");
-  TORCH_CHECK(preds_in.device() == target_in.device(), "vif_sums: preds and target on different devices");
-  TORCH_CHECK(preds_in.dim() == 3 && preds_in.sizes() == target_in.sizes(), "vif_sums: expected matching [P, H, W]");
-  TORCH_CHECK(preds_in.scalar_type() == target_in.scalar_type(), "vif_sums: dtype mismatch");
-  const auto dtype = preds_in.scalar_type();
-  TORCH_CHECK(dtype == at::kFloat || dtype == at::kBFloat16 || dtype == at::kHalf, "vif_sums: unsupported dtype ", dtype);
+  at::Tensor p, t;
+  std::tie(p, t) = checked_pair(preds_in, target_in, 3, "[P, H, W]", "vif_sums");
   TORCH_CHECK(sigma_n_sq > 0, "vif_sums: sigma_n_sq must be positive");
-  const int64_t P = preds_in.size(0), H = preds_in.size(1), W = preds_in.size(2);
+  const int64_t P = p.size(0), H = p.size(1), W = p.size(2);
   TORCH_CHECK(H >= 41 && W >= 41, "vif_sums: planes smaller than 41 x 41");
   TORCH_CHECK(H * W <= INT32_MAX, "vif_sums: plane too large");
-  const at::DeviceGuard guard(preds_in.device());
-  auto p = preds_in.contiguous();
-  auto t = target_in.contiguous();
+  const at::DeviceGuard guard(p.device());
   auto opts = p.options().dtype(at::kDouble);
   if (P == 0) return at::zeros({kVifScales, 2, 0}, opts);
 
@@ -314,7 +308,7 @@ at::Tensor vif_sums(const at::Tensor& preds_in, const at::Tensor& target_in, dou
   const float sn = static_cast<float>(sigma_n_sq);
   double* part = partial.data_ptr<double>();
   float* lv = levels.data_ptr<float>();
-  dispatch_float3(dtype, "vif_sums", [&](auto tag) { vif_run<decltype(tag)>(p, t, sn, h, w, tiles_h, tiles_w, offset, part, lv); });
+  dispatch_float3(p.scalar_type(), "vif_sums", [&](auto tag) { vif_run<decltype(tag)>(p, t, sn, h, w, tiles_h, tiles_w, offset, part, lv); });
   hipLaunchKernelGGL(vif_fold_kernel, dim3(static_cast<unsigned>(2 * kVifScales * P)), dim3(kWave), 0, stream(), part, fold,
                      static_cast<int>(P), out.data_ptr<double>());
   TMX_LAUNCH_CHECK();

@@ -292,3 +292,49 @@ def test_kid_poly_sums_route(d, want, unwanted):
     ref = torch.stack([kxx.sum() - kxx.diag().sum(), kyy.sum() - kyy.diag().sum(), kxy.sum()])
     torch.testing.assert_close(sums, ref, rtol=2e-5, atol=2e-5 * m * m)  # (test_kid_poly_sums_vs_torch's fp32 bound)
     assert_route(names, present=[want], absent=[unwanted])
+
+
+# ------------------------------------------------------------------------------------------- host checks of the pair ops
+# The checks the two-tensor entry points open with (csrc/common.h checked_pair): the op's name and the phrase, as the sources had
+# them before the checks were shared.  Every call raises ahead of any launch.  (tmx::signal_pair_ratios:
+# tests/test_signal_pairs_gpu.py::test_host_checks.)
+def _pair_op_cases():
+    t = torch.ops.tmx
+    win = lambda dev: torch.ones(3, device=dev) / 3
+    return {
+        "sdr_scores": (3, "[G, S, T]", lambda p, q: t.sdr_scores(p, q, 2, False, None, 0)),
+        "sdr_correlations": (3, "[G, S, T]", lambda p, q: t.sdr_correlations(p, q, 2, False, 0)),
+        "sam_map": (4, "[B, C, H, W]", lambda p, q: t.sam_map(p, q)),
+        "sam_sums": (4, "[B, C, H, W]", lambda p, q: t.sam_sums(p, q)),
+        "ergas_scores": (4, "[B, C, H, W]", lambda p, q: t.ergas_scores(p, q, 4.0)),
+        "box_rmse_maps": (4, "[B, C, H, W]", lambda p, q: t.box_rmse_maps(p, q, 2, 1, False)),
+        "uqi_sums": (3, "[P, H, W]", lambda p, q: t.uqi_sums(p, q, win(p.device), win(p.device), 1e-8)),
+        "vif_sums": (3, "[P, H, W]", lambda p, q: t.vif_sums(p, q, 2.0)),
+    }
+
+
+@pytest.mark.parametrize("name", ["sdr_scores", "sdr_correlations", "sam_map", "sam_sums", "ergas_scores", "box_rmse_maps", "uqi_sums", "vif_sums"])
+def test_pair_op_host_checks(name):
+    import re
+
+    rank, layout, call = _pair_op_cases()[name]
+    p = torch.rand(*(2, 2, 3, 3)[-rank:], device="cuda")
+    bad = [
+        (p, p.cpu(), "expected GPU tensors"),
+        (p.cpu(), p, "expected GPU tensors"),
+        (p, p.half(), "dtype mismatch"),
+        (p.double(), p.double(), "unsupported dtype Double"),
+        (p, p[..., :2], "expected matching " + layout),
+        (p[0], p[0], "expected matching " + layout),
+    ]
+    if name not in ("uqi_sums", "vif_sums"):
+        bad.append((p[:0], p[:0], "empty input"))
+    for a, b, phrase in bad:
+        with pytest.raises(RuntimeError, match=re.escape(f"{name}: {phrase}")):
+            call(a, b)
+    # no plane is no error for the two window ops: an empty result, no launch
+    if name == "uqi_sums":
+        assert call(p[:0], p[:0]).shape == (0,)
+    if name == "vif_sums":
+        e = torch.rand(0, 41, 41, device="cuda")
+        assert call(e, e).shape == (4, 2, 0)

@@ -74,3 +74,97 @@ def test_cpu_5d_fp32_never_native(monkeypatch):
     p, t = _volumes((1, 1, 12, 13, 14), 4)
     out = ssim_mod.structural_similarity_index_measure(p.float(), t.float(), sigma=0.8, data_range=1.0)
     assert out.dtype == torch.float32 and torch.isfinite(out)
+
+
+class _OnGpu(torch.Tensor):
+    """A plain CPU tensor that answers ``is_cuda`` with True: reaches the gates' later arms without a GPU."""
+
+    is_cuda = property(lambda self: True)
+
+
+def _gpu_like(*shape, dtype=torch.float32):
+    return torch.rand(*shape).to(dtype).as_subclass(_OnGpu)
+
+
+def _spy_use_native(monkeypatch):
+    seen = []
+
+    def use_native(*tensors):
+        seen.append(tensors)
+        return True
+
+    monkeypatch.setattr(ssim_mod.ops, "use_native", use_native)
+    monkeypatch.delenv("TMX_SSIM3D_NATIVE", raising=False)
+    monkeypatch.delenv("TMX_SSIM_NATIVE_GRAD", raising=False)
+    return seen, use_native
+
+
+def test_2d_gate_arm_by_arm(monkeypatch):
+    ok = ssim_mod._native_ssim_ok
+    seen, use_native = _spy_use_native(monkeypatch)
+    p, t = _gpu_like(2, 3, 20, 21), _gpu_like(2, 3, 20, 21)
+    assert ok(p, t, (11, 11), False) and len(seen) == 1 and len(seen[0]) == 1 and seen[0][0] is p  # preds alone is handed on
+    assert ok(_gpu_like(2, 3, 20, 21, dtype=torch.float64), _gpu_like(2, 3, 20, 21, dtype=torch.float64), (11, 11), False)
+    # device, rank, the full image
+    assert not ok(torch.rand(2, 3, 20, 21), t, (11, 11), False)
+    assert not ok(_gpu_like(3, 20, 21), _gpu_like(3, 20, 21), (11, 11), False)
+    assert not ok(_gpu_like(1, 2, 3, 20, 21), _gpu_like(1, 2, 3, 20, 21), (11, 11), False)
+    assert not ok(p, t, (11, 11), True)
+    # a square window of the native set that fits the plane
+    assert all(ok(p, t, (k, k), False) for k in (3, 5, 7, 9, 11, 13, 15))
+    assert not ok(p, t, (11, 9), False) and not ok(p, t, (1, 1), False) and not ok(p, t, (17, 17), False) and not ok(p, t, (4, 4), False)
+    assert ok(_gpu_like(1, 1, 11, 11), _gpu_like(1, 1, 11, 11), (11, 11), False)
+    assert not ok(_gpu_like(1, 1, 10, 11), _gpu_like(1, 1, 10, 11), (11, 11), False)
+    assert not ok(_gpu_like(1, 1, 11, 10), _gpu_like(1, 1, 11, 10), (11, 11), False)
+    # autograd has a native backward: constant c1 / c2, the 32- and 16-bit float types, and its knob, read on every call
+    pg = _gpu_like(2, 3, 20, 21).requires_grad_()
+    assert ok(pg, t, (11, 11), False) and ok(t, pg, (11, 11), False)
+    assert not ok(pg, t, (11, 11), False, True) and not ok(t, pg, (11, 11), False, input_range=True)
+    p64 = _gpu_like(2, 3, 20, 21, dtype=torch.float64).requires_grad_()
+    assert not ok(p64, p64.detach(), (11, 11), False)
+    n = len(seen)
+    monkeypatch.setenv("TMX_SSIM_NATIVE_GRAD", "0")
+    assert not ok(pg, t, (11, 11), False) and len(seen) == n
+    assert ok(p, t, (11, 11), False)  # the knob binds the gradient route only
+    with torch.no_grad():
+        assert ok(pg, t, (11, 11), False, True) and ok(p64, p64, (11, 11), False)
+    # the library's own answer
+    monkeypatch.setattr(ssim_mod.ops, "use_native", lambda *a: False)
+    assert not ok(p, t, (11, 11), False)
+
+
+def test_3d_gate_arm_by_arm(monkeypatch):
+    ok = ssim_mod._native_ssim3d_ok
+    seen, use_native = _spy_use_native(monkeypatch)
+    p, t = _gpu_like(1, 2, 12, 13, 14), _gpu_like(1, 2, 12, 13, 14)
+    w = (11, 11, 11)
+    assert ok(p, t, w, w, False) and len(seen) == 1 and seen[0][0] is p and seen[0][1] is t
+    for dtype in (torch.bfloat16, torch.float16):
+        assert ok(_gpu_like(1, 1, 12, 13, 14, dtype=dtype), _gpu_like(1, 1, 12, 13, 14, dtype=dtype), w, w, False)
+    assert ok(p, t, (3, 5, 7), (3, 5, 7), False)  # one window per axis
+    # device, rank, the full image
+    assert not ok(torch.rand(1, 2, 12, 13, 14), t, w, w, False)
+    assert not ok(_gpu_like(2, 12, 13, 14), _gpu_like(2, 12, 13, 14), w, w, False) and not ok(p, t, w, w, True)
+    # autograd on either side, under grad mode
+    pg = _gpu_like(1, 2, 12, 13, 14).requires_grad_()
+    assert not ok(pg, t, w, w, False) and not ok(t, pg, w, w, False)
+    with torch.no_grad():
+        assert ok(pg, t, w, w, False)
+    # dtype and empty
+    assert not ok(_gpu_like(1, 2, 12, 13, 14, dtype=torch.float64), _gpu_like(1, 2, 12, 13, 14, dtype=torch.float64), w, w, False)
+    assert not ok(_gpu_like(0, 2, 12, 13, 14), _gpu_like(0, 2, 12, 13, 14), w, w, False)
+    # per axis: a window of the native set, a pad of at least one, a dim not below its window and above its pad
+    assert not ok(p, t, (11, 11, 17), (11, 11, 17), False) and not ok(p, t, (11, 4, 11), (11, 4, 11), False)
+    assert not ok(p, t, (11, 11, 3), (11, 11, 1), False)  # zero pad
+    assert not ok(p, t, (13, 11, 11), (13, 11, 11), False) and ok(p, t, (11, 13, 13), (11, 13, 13), False)  # D = 12 below a window of 13
+    assert not ok(_gpu_like(1, 1, 12, 13, 5), _gpu_like(1, 1, 12, 13, 5), (11, 11, 3), (11, 11, 11), False)  # W = 5 is the pad of 11
+    assert ok(_gpu_like(1, 1, 12, 13, 6), _gpu_like(1, 1, 12, 13, 6), (11, 11, 3), (11, 11, 11), False)
+    # the library's own answer, and the knob, which is read on every call
+    n = len(seen)
+    monkeypatch.setattr(ssim_mod.ops, "use_native", lambda *a: False)
+    assert not ok(p, t, w, w, False)
+    monkeypatch.setattr(ssim_mod.ops, "use_native", use_native)
+    monkeypatch.setenv("TMX_SSIM3D_NATIVE", "0")
+    assert not ok(p, t, w, w, False) and len(seen) == n
+    monkeypatch.setenv("TMX_SSIM3D_NATIVE", "1")
+    assert ok(p, t, w, w, False) and len(seen) == n + 1

@@ -76,3 +76,56 @@ def test_module():
     assert torch.equal(fresh.compute(), m.compute())
     m.update(p[1:2], t[1:2])  # a non-empty mask against an empty one
     assert float(m.compute()) == float("inf")
+
+
+class _OnGpu(torch.Tensor):
+    """A plain CPU tensor that answers ``is_cuda`` with True: reaches the gate's later arms without a GPU."""
+
+    is_cuda = property(lambda self: True)
+
+
+def _gpu_like(*shape, dtype=torch.int64):
+    return torch.randint(0, 2, shape).to(dtype).as_subclass(_OnGpu)
+
+
+def test_gate_arm_by_arm(monkeypatch):
+    import sys
+
+    hd_mod = sys.modules["torchmetrics_forked_amd.functional.segmentation.hausdorff_distance"]
+    ok = hd_mod._native_hausdorff_ok
+    seen = []
+
+    def use_native(*tensors):
+        seen.append(tensors)
+        return True
+
+    monkeypatch.setattr(hd_mod.ops, "use_native", use_native)
+    monkeypatch.setattr(hd_mod, "_HAUSDORFF_NATIVE", True)
+    p, t = _gpu_like(2, 8, 9), _gpu_like(2, 8, 9, dtype=torch.uint8)  # the two sides need not share a dtype
+    assert ok(p, t, "index") and len(seen) == 1 and seen[0][0] is p and seen[0][1] is t
+    for dtype in (torch.uint8, torch.int16, torch.int32, torch.int64):
+        assert ok(_gpu_like(2, 8, 9, dtype=dtype), p, "index")
+    for dtype in (torch.bool, torch.uint8, torch.int32, torch.int64):
+        assert ok(_gpu_like(2, 3, 8, 9, dtype=dtype), _gpu_like(2, 3, 8, 9), "one-hot")
+    # device
+    host = torch.zeros(2, 8, 9, dtype=torch.int64)
+    assert not ok(host, host, "index") and not ok(p, host, "index") and not ok(host, t, "index")
+    # dtype: each form has its own set
+    assert not ok(_gpu_like(2, 8, 9, dtype=torch.int8), p, "index") and not ok(p, _gpu_like(2, 8, 9, dtype=torch.bool), "index")
+    assert not ok(_gpu_like(2, 3, 8, 9, dtype=torch.int16), _gpu_like(2, 3, 8, 9), "one-hot")
+    assert not ok(_gpu_like(2, 3, 8, 9), _gpu_like(2, 3, 8, 9, dtype=torch.int8), "one-hot")
+    # the plane: not empty, and within the op's extents (expanded views, no storage behind them)
+    assert not ok(_gpu_like(2, 0, 9), _gpu_like(2, 0, 9), "index") and not ok(_gpu_like(2, 8, 0), _gpu_like(2, 8, 0), "index")
+    assert ok(_gpu_like(0, 8, 9), _gpu_like(0, 8, 9), "index")  # no sample: the op's own matter
+    max_h, max_w = hd_mod._HAUSDORFF_MAX_H, hd_mod._HAUSDORFF_MAX_W
+    tall = lambda h: torch.zeros(1, 1, 1, dtype=torch.int64).expand(1, h, 2).as_subclass(_OnGpu)
+    wide = lambda w: torch.zeros(1, 1, 1, dtype=torch.int64).expand(1, 2, w).as_subclass(_OnGpu)
+    assert ok(tall(max_h), tall(max_h), "index") and not ok(tall(max_h + 1), tall(max_h + 1), "index")
+    assert ok(wide(max_w), wide(max_w), "index") and not ok(wide(max_w + 1), wide(max_w + 1), "index")
+    # the library's own answer and the knob
+    n = len(seen)
+    monkeypatch.setattr(hd_mod.ops, "use_native", lambda *a: False)
+    assert not ok(p, t, "index")
+    monkeypatch.setattr(hd_mod.ops, "use_native", use_native)
+    monkeypatch.setattr(hd_mod, "_HAUSDORFF_NATIVE", False)
+    assert not ok(p, t, "index") and len(seen) == n

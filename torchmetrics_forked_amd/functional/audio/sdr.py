@@ -39,36 +39,18 @@ _SDR_MAX_FILTER = 2048  # ``ops.audio.sdr_tile()[3]`` (the library is not asked 
 
 def _native_signal_ok(preds: Tensor, target: Tensor) -> bool:
     """Route to ``tmx::signal_pair_ratios``; everything else keeps the composition."""
-    if not (preds.is_cuda and target.is_cuda):
-        return False
-    if preds.dtype != target.dtype or preds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    if preds.is_complex() or target.is_complex():
-        return False
-    if preds.ndim < 1 or preds.shape != target.shape or preds.numel() == 0:
-        return False
-    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
-        return False
-    return _AUDIO_NATIVE and ops.use_native(preds, target)
+    return preds.ndim >= 1 and _AUDIO_NATIVE and ops.native_inputs_ok(preds, target)
 
 
 def _native_sdr_ok(preds: Tensor, target: Tensor, filter_length: int) -> bool:
     """Route ``signal_distortion_ratio`` to ``tmx::sdr_scores``; everything else keeps ``_sdr_composition``."""
-    if not (preds.is_cuda and target.is_cuda):
-        return False
-    if preds.dtype != target.dtype or preds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    if preds.ndim < 1 or preds.shape != target.shape or preds.numel() == 0:
-        return False
     try:
         length = operator.index(filter_length)  # Python and NumPy integers alike
     except TypeError:
         return False
-    if not 1 <= length <= _SDR_MAX_FILTER:
+    if preds.ndim < 1 or not 1 <= length <= _SDR_MAX_FILTER:
         return False
-    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
-        return False
-    return _SDR_NATIVE and ops.use_native(preds, target)
+    return _SDR_NATIVE and ops.native_inputs_ok(preds, target)
 
 
 def _native_row_ratios(preds: Tensor, target: Tensor, scale_invariant: bool, zero_mean: bool) -> Tensor:

@@ -191,11 +191,12 @@ def _native_srmr_ok(preds: Tensor, fs: int, fast: bool = False) -> bool:
     Everything else keeps the composition: CPU tensors, integer inputs, ``fast=True``, inputs that require grad, empty or too short
     inputs.  (An argument set whose ``kstar`` table has an invalid entry is sent back by the caller, which has the table.)  No shape
     class is routed back: the native route was the faster one at every shape measured."""
-    if not preds.is_cuda or fast or preds.dtype not in _NATIVE_DTYPES or preds.requires_grad:
+    # ``requires_grad`` alone keeps the composition, whatever the grad mode (the shared rule would admit such an input under ``no_grad``)
+    if fast or preds.requires_grad:
         return False
-    if preds.dim() < 1 or preds.numel() == 0 or preds.shape[-1] < ceil(0.256 * fs):
+    if preds.dim() < 1 or preds.shape[-1] < ceil(0.256 * fs):
         return False
-    return _SRMR_NATIVE and ops.use_native(preds)
+    return _SRMR_NATIVE and ops.native_inputs_ok(preds, dtypes=_NATIVE_DTYPES)  # fp64 is taken too
 
 
 def _srmr_native(preds: Tensor, fs: int, tables: "_audio_ops.SrmrTables", norm: bool) -> Tensor:

@@ -189,13 +189,10 @@ def _native_stoi_ok(preds: Tensor, target: Tensor, fs: int) -> bool:
     """Route to ``tmx::stoi_scores``: GPU tensors of one dtype among fp32 / fp64 / bf16 / fp16 with at least one signal and one
     sample, an integer ``fs > 0``, ``TMX_STOI_NATIVE`` (read once per process) not ``0``.  Everything else keeps the composition:
     CPU tensors, empty inputs, other or mixed dtypes.  No rate is routed back: the kernels take every ratio ``10000 / fs``."""
-    if not (preds.is_cuda and target.is_cuda):
+    if preds.dim() < 1 or not isinstance(fs, int) or isinstance(fs, bool) or fs <= 0:
         return False
-    if preds.dtype != target.dtype or preds.dtype not in _NATIVE_DTYPES:
-        return False
-    if preds.dim() < 1 or preds.numel() == 0 or not isinstance(fs, int) or isinstance(fs, bool) or fs <= 0:
-        return False
-    return _STOI_NATIVE and ops.use_native(preds, target)
+    # fp64 is taken too, and the signals are detached before the call: an input that records autograd is admitted
+    return _STOI_NATIVE and ops.native_inputs_ok(preds, target, dtypes=_NATIVE_DTYPES, grad_ok=True)
 
 
 def _warn_short(frames: List[int]) -> None:

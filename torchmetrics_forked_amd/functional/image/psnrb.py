@@ -26,15 +26,9 @@ def _native_psnrb_ok(preds: Tensor, target: Tensor) -> bool:
 
     No shape class is routed back: the native route is the faster one on every shape of ``tools/gradient_bench.py``
     (``profiles/gradient_bench.json``)."""
-    if not (preds.is_cuda and target.is_cuda) or preds.shape != target.shape:
+    if preds.ndim != 4 or preds.size(1) != 1 or preds.size(2) < 2 or preds.size(3) < 2:
         return False
-    if preds.dtype != target.dtype or preds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    if preds.ndim != 4 or preds.numel() == 0 or preds.size(1) != 1 or preds.size(2) < 2 or preds.size(3) < 2:
-        return False
-    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
-        return False
-    return _GRADIENT_NATIVE and ops.use_native(preds, target)
+    return _GRADIENT_NATIVE and ops.native_inputs_ok(preds, target)
 
 
 def _psnrb_native_update(preds: Tensor, target: Tensor, block_size: int) -> Tuple[Tensor, Tensor, int, Tensor]:

@@ -37,7 +37,9 @@ def _rase_update(
 
 
 def _native_rase_fold_ok(rmse_map: Tensor, target_sum: Tensor, total_images: Tensor, window_size: int) -> bool:
-    """Route ``_rase_compute`` to ``tmx::rase_fold``: GPU maps of one fp32 / bf16 / fp16 dtype with a non-empty crop, no autograd."""
+    """Route ``_rase_compute`` to ``tmx::rase_fold``: GPU maps of one fp32 / bf16 / fp16 dtype with a non-empty crop, no autograd.
+
+    Spelled out here, not through ``ops.native_inputs_ok``: the image count is a third tensor of its own shape and dtype."""
     if not (rmse_map.is_cuda and target_sum.is_cuda and total_images.is_cuda) or rmse_map.ndim != 3:
         return False
     if rmse_map.shape != target_sum.shape or rmse_map.dtype != target_sum.dtype:

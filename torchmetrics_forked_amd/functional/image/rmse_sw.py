@@ -27,18 +27,12 @@ def _native_rmse_sw_ok(preds: Tensor, target: Tensor, window_size: int) -> bool:
     No shape class is routed back: on every shape of ``tools/box_bench.py`` the native route is the faster one, from 2.5x at
     32 x 1 x 41 x 41 to 14x (RMSE-SW) and 15x (RASE) at 1024 x 1024 with window 8 and 31x / 38x with window 15
     (``profiles/box_bench.json``)."""
-    if not (preds.is_cuda and target.is_cuda) or preds.ndim != 4 or preds.shape != target.shape:
-        return False
-    if preds.dtype != target.dtype or preds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
-        return False
-    if not 2 <= window_size <= 16:
+    if preds.ndim != 4 or not 2 <= window_size <= 16:
         return False
     crop = round(window_size / 2)
-    if preds.numel() == 0 or preds.size(-2) <= 2 * crop or preds.size(-1) <= 2 * crop:
+    if preds.size(-2) <= 2 * crop or preds.size(-1) <= 2 * crop:
         return False
-    return _BOX_NATIVE and ops.use_native(preds, target)
+    return _BOX_NATIVE and ops.native_inputs_ok(preds, target)
 
 
 def _rmse_sw_validate(preds: Tensor, target: Tensor, window_size: int) -> None:

@@ -28,15 +28,9 @@ def _native_sam_ok(preds: Tensor, target: Tensor) -> bool:
 
     No shape class is routed back: the native route is the faster one on every shape of ``tools/spectral_bench.py``
     (``profiles/spectral_bench.json``)."""
-    if not (preds.is_cuda and target.is_cuda) or preds.shape != target.shape:
+    if preds.ndim != 4 or preds.size(1) < 2:
         return False
-    if preds.dtype != target.dtype or preds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    if preds.ndim != 4 or preds.size(1) < 2 or preds.numel() == 0:
-        return False
-    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
-        return False
-    return _SPECTRAL_NATIVE and ops.use_native(preds, target)
+    return _SPECTRAL_NATIVE and ops.native_inputs_ok(preds, target)
 
 
 def _sam_update(preds: Tensor, target: Tensor) -> Tuple[Tensor, Tensor]:

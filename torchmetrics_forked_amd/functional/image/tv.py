@@ -8,7 +8,6 @@ before the gate."""
 import os
 from typing import Optional, Tuple, Union
 
-import torch
 from torch import Tensor
 from typing_extensions import Literal
 
@@ -23,13 +22,7 @@ def _native_tv_ok(img: Tensor) -> bool:
 
     No shape class is routed back: the native route is the faster one on every shape of ``tools/gradient_bench.py``
     (``profiles/gradient_bench.json``)."""
-    if not img.is_cuda or img.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    if img.ndim != 4 or img.numel() == 0:
-        return False
-    if torch.is_grad_enabled() and img.requires_grad:
-        return False
-    return _GRADIENT_NATIVE and ops.use_native(img)
+    return img.ndim == 4 and _GRADIENT_NATIVE and ops.native_inputs_ok(img)
 
 
 def _total_variation_update(img: Tensor) -> Tuple[Tensor, int]:

@@ -66,15 +66,9 @@ def _vif_planes(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:
 
 def _native_vif_ok(preds: Tensor, target: Tensor, sigma_n_sq: float) -> bool:
     """Route to ``tmx::vif_sums``; everything else keeps the composition."""
-    if not (preds.is_cuda and target.is_cuda) or preds.ndim != 4 or preds.shape != target.shape:
+    if preds.ndim != 4 or preds.size(-1) < 41 or preds.size(-2) < 41 or not sigma_n_sq > 0:
         return False
-    if preds.dtype != target.dtype or preds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return False
-    if torch.is_grad_enabled() and (preds.requires_grad or target.requires_grad):
-        return False
-    if preds.numel() == 0 or preds.size(-1) < 41 or preds.size(-2) < 41 or not sigma_n_sq > 0:
-        return False
-    return _VIF_NATIVE and ops.use_native(preds, target)
+    return _VIF_NATIVE and ops.native_inputs_ok(preds, target)
 
 
 def _vif_plane_scores(preds: Tensor, target: Tensor, sigma_n_sq: float) -> Tensor:

@@ -29,32 +29,34 @@ _LABEL_CAP = 64
 _WORD = (1 << 64) - 1
 
 
+def _labels_ok(*tensors: Tensor) -> bool:
+    """The shared rule with this family's dtypes.  The values are category labels or counts and the result carries no graph, so an fp32
+    input that records autograd is admitted as before."""
+    return ops.native_inputs_ok(*tensors, dtypes=_NATIVE_DTYPES, grad_ok=True)
+
+
 def _native_nominal_ok(matrix: Tensor) -> bool:
     """The gate of the ``*_matrix`` route: a non-empty 2-D GPU matrix of int64, int32 or fp32 with at least two columns and fewer than
     ``2**31`` rows, the knob not switched off, and the native library in use."""
-    if not (isinstance(matrix, Tensor) and matrix.is_cuda and matrix.ndim == 2 and matrix.dtype in _NATIVE_DTYPES and matrix.numel() > 0):
+    if not (isinstance(matrix, Tensor) and matrix.ndim == 2) or matrix.shape[1] < 2 or matrix.shape[0] >= 2**31:
         return False
-    if matrix.shape[1] < 2 or matrix.shape[0] >= 2**31:
-        return False
-    return _NOMINAL_NATIVE and ops.use_native(matrix)
+    return _NOMINAL_NATIVE and _labels_ok(matrix)
 
 
 def _native_pair_ok(preds: Tensor, target: Tensor) -> bool:
     """Two 1-D GPU tensors of one supported dtype and one length; 2-D inputs (the argmax path) and mixed dtypes keep the composition."""
-    if not (isinstance(preds, Tensor) and isinstance(target, Tensor) and preds.is_cuda and target.is_cuda):
+    if not (isinstance(preds, Tensor) and isinstance(target, Tensor)) or preds.ndim != 1 or preds.numel() >= 2**31:
         return False
-    if preds.ndim != 1 or target.ndim != 1 or preds.shape != target.shape or preds.dtype != target.dtype or preds.device != target.device:
+    if preds.device != target.device:  # two GPUs keep the composition here; ``use_native`` would raise
         return False
-    return preds.dtype in _NATIVE_DTYPES and 0 < preds.numel() < 2**31 and _NOMINAL_NATIVE and ops.use_native(preds, target)
+    return _NOMINAL_NATIVE and _labels_ok(preds, target)
 
 
 def _native_scores_ok(confmat: Tensor) -> bool:
     """The gate of the modules' ``compute()``: a square GPU state of at most 64 categories."""
-    if not (isinstance(confmat, Tensor) and confmat.is_cuda and confmat.ndim == 2 and confmat.dtype in _NATIVE_DTYPES):
+    if not (isinstance(confmat, Tensor) and confmat.ndim == 2) or confmat.shape[0] != confmat.shape[1] or confmat.shape[0] > _LABEL_CAP:
         return False
-    if confmat.shape[0] != confmat.shape[1] or not 0 < confmat.shape[0] <= _LABEL_CAP:
-        return False
-    return _NOMINAL_NATIVE and ops.use_native(confmat)
+    return _NOMINAL_NATIVE and _labels_ok(confmat)
 
 
 def _masks_dense(masks: Sequence[int]) -> bool:

@@ -12,7 +12,7 @@ Policy (MI355X-first, no silent fallbacks on the GPU):
 import os
 import threading
 from pathlib import Path
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -102,6 +102,27 @@ def use_native(t: torch.Tensor, *others: Optional[torch.Tensor]) -> bool:
         if isinstance(o, torch.Tensor) and o.is_cuda:
             raise _device_error(o.device, t.device)
     return False
+
+
+NATIVE_FLOATS = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def native_inputs_ok(*tensors: torch.Tensor, dtypes: Tuple[torch.dtype, ...] = NATIVE_FLOATS, grad_ok: bool = False) -> bool:
+    """The admission rule the native routes share, stated once: every tensor on the GPU, all of one shape and of one dtype among
+    ``dtypes``, not empty, none recording autograd under grad mode, and then :func:`use_native` on the same tensors in the same order.
+
+    A gate tests its op's own conditions and its A/B knob first and ends in this call, so :func:`use_native`, which raises for tensors
+    on two devices, is reached only after every other condition held.  ``grad_ok``: the op detaches its inputs or its result carries no
+    graph by design, so an input that records is admitted."""
+    first = tensors[0]
+    for t in tensors:
+        if not t.is_cuda or t.shape != first.shape or t.dtype != first.dtype:
+            return False
+    if first.dtype not in dtypes or first.numel() == 0:
+        return False
+    if not grad_ok and torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return False
+    return use_native(*tensors)
 
 
 def lib_path() -> Path:
