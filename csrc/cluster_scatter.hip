@@ -21,7 +21,7 @@
 // row's Dp lanes, then per row d^2 (CH), d (DB) or the p-norm (Dunn).  CH needs only the total and Dunn only the largest
 // radius, so they keep one register per slot; DB keeps acc[cluster][slot] in LDS over a cluster window.  One partial per
 // workgroup; cluster_score_kernel folds them in order and evaluates the composition's formula and edge rules in fp64.
-#include "common.h"
+#include "cluster.h"
 
 #include <cstdlib>
 #include <limits>

@@ -7,7 +7,7 @@
 //       * exp(lgamma(a_i+1) + lgamma(b_j+1) + lgamma(N-a_i+1) + lgamma(N-b_j+1) - lgamma(N+1)
 //             - lgamma(n_ij+1) - lgamma(a_i-n_ij+1) - lgamma(b_j-n_ij+1) - lgamma(N-a_i-b_j+n_ij+1)).
 // The pair sums land in a [R * K] buffer that the host reduces in a fixed order (deterministic result).
-#include "common.h"
+#include "cluster.h"
 
 namespace tmx {
 namespace {

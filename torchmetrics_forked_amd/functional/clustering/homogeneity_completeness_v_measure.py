@@ -1,12 +1,12 @@
 """Homogeneity / completeness / V-measure (API parity: reference
 ``functional/clustering/homogeneity_completeness_v_measure.py``)."""
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from torchmetrics_forked_amd.functional.clustering.mutual_info_score import mutual_info_score
-from torchmetrics_forked_amd.functional.clustering.utils import calculate_entropy, check_cluster_labels
+from torchmetrics_forked_amd.functional.clustering.utils import _native_extrinsic, calculate_entropy, check_cluster_labels
 
 
 def _homogeneity_score_compute(preds: Tensor, target: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
@@ -26,15 +26,29 @@ def _completeness_score_compute(preds: Tensor, target: Tensor) -> Tuple[Tensor, 
     return completeness, homogeneity
 
 
+def _native_score(preds: Tensor, target: Tensor, metric: str, beta: float = 1.0) -> Optional[Tensor]:
+    check_cluster_labels(preds, target)
+    return _native_extrinsic(preds, target, metric, beta=beta)
+
+
 def homogeneity_score(preds: Tensor, target: Tensor) -> Tensor:
+    native = _native_score(preds, target, "homogeneity")
+    if native is not None:
+        return native
     return _homogeneity_score_compute(preds, target)[0]
 
 
 def completeness_score(preds: Tensor, target: Tensor) -> Tensor:
+    native = _native_score(preds, target, "completeness")
+    if native is not None:
+        return native
     return _completeness_score_compute(preds, target)[0]
 
 
 def v_measure_score(preds: Tensor, target: Tensor, beta: float = 1.0) -> Tensor:
+    native = _native_score(preds, target, "v_measure", beta)
+    if native is not None:
+        return native
     completeness, homogeneity = _completeness_score_compute(preds, target)
     if homogeneity + completeness == 0.0:
         return torch.ones_like(homogeneity)

@@ -1,11 +1,15 @@
-"""Python entry points for ``csrc/clustering.hip`` (expected mutual information on the GPU) and
-``csrc/cluster_scatter.hip`` (label ranks, segmented sums, scatter and score of the intrinsic clustering metrics)."""
-from typing import Dict, Tuple
+"""Python entry points for ``csrc/clustering.hip`` (expected mutual information on the GPU),
+``csrc/cluster_scatter.hip`` (label ranks, segmented sums, scatter and score of the intrinsic clustering metrics) and
+``csrc/cluster_pairs.hip`` (pair table, table statistics and score of the extrinsic clustering metrics)."""
+from typing import Dict, Optional, Tuple
 
 from torch import Tensor
 import torch
 
 CLUSTER_METRICS = {"calinski_harabasz": 0, "davies_bouldin": 1, "dunn": 2}
+CLUSTER_PAIR_METRICS = {"mutual_info": 0, "normalized_mutual_info": 1, "adjusted_mutual_info": 2, "rand": 3, "adjusted_rand": 4,
+                        "fowlkes_mallows": 5, "homogeneity": 6, "completeness": 7, "v_measure": 8}
+CLUSTER_PAIR_AVERAGES = {"min": 0, "geometric": 1, "arithmetic": 2, "max": 3}
 
 
 def expected_mutual_info(a: Tensor, b: Tensor, n_samples: int) -> Tensor:
@@ -54,3 +58,54 @@ def cluster_intrinsic_score(data: Tensor, inv: Tensor, k: int, metric: str, p: f
     if data.dtype == torch.float32 or (metric != "dunn" and bool(res[1])):
         return resf.reshape(())
     return res[0].to(data.dtype)
+
+
+def cluster_pair_tile() -> Dict[str, int]:
+    """Constants of the pair-table kernel: workgroup threads, u32 cells of the LDS arm (``lds_cells``), ranks per lane and
+    step, the most replicas of a small table, the largest table of the global arm and the largest ``K`` per side."""
+    _require()
+    return dict(zip(("threads", "lds_cells", "per_lane", "replica_cap", "cell_cap", "cap"), (int(v) for v in torch.ops.tmx.cluster_pair_tile())))
+
+
+def cluster_pair_rows_per_chunk(n: int, cells: int) -> int:
+    """Label pairs one workgroup of the pair-table kernel walks for ``n`` pairs and a table of ``cells`` cells (shape alone)."""
+    _require()
+    return int(torch.ops.tmx.cluster_pair_rows_per_chunk(int(n), int(cells)))
+
+
+def _pair_ranks(preds: Tensor, target: Tensor) -> Tuple[Tensor, Tensor, int, int]:
+    """int32 ranks of both label vectors and their cluster counts.  One host read: ``(K_p, wide_p, K_t, wide_t)``.
+    A side spanning 2^20 or more takes ``torch.unique``'s inverse and continues natively."""
+    inv_p, inv_t, info = torch.ops.tmx.cluster_pair_ranks(preds, target)
+    kp, wide_p, kt, wide_t = info.tolist()
+    if wide_p:
+        uniq, inv = torch.unique(preds, return_inverse=True)
+        inv_p, kp = inv.to(torch.int32), len(uniq)
+    if wide_t:
+        uniq, inv = torch.unique(target, return_inverse=True)
+        inv_t, kt = inv.to(torch.int32), len(uniq)
+    return inv_p, inv_t, kp, kt
+
+
+def _pair_table(preds: Tensor, target: Tensor) -> Optional[Tensor]:
+    inv_p, inv_t, kp, kt = _pair_ranks(preds, target)
+    cap = cluster_pair_tile()["cap"]
+    if kp > cap or kt > cap:
+        return None
+    return torch.ops.tmx.cluster_pair_table(inv_p, inv_t, kp, kt)
+
+
+def cluster_pair_table(preds: Tensor, target: Tensor) -> Optional[Tensor]:
+    """The int64 ``[K_target, K_preds]`` contingency table of two integer label vectors ``[N]`` on one GPU (widened from
+    the kernel's int32: ``N < 2^31``), or None when a side has more clusters than ``cluster_pair_tile()["cap"]``."""
+    table = _pair_table(preds, target)
+    return None if table is None else table.long()
+
+
+def cluster_extrinsic_score(preds: Tensor, target: Tensor, metric: str, average_method: str = "arithmetic", beta: float = 1.0) -> Optional[Tensor]:
+    """The 0-dim fp32 score ``metric`` (a key of ``CLUSTER_PAIR_METRICS``) of two integer label vectors ``[N]`` on one
+    GPU, or None when a side has more clusters than the cap.  One host read per call (the two ``(K, wide)`` pairs)."""
+    table = _pair_table(preds, target)
+    if table is None:
+        return None
+    return torch.ops.tmx.cluster_pair_score(table, preds.numel(), CLUSTER_PAIR_METRICS[metric], CLUSTER_PAIR_AVERAGES[average_method], float(beta))
