@@ -4,6 +4,8 @@ Backbones come from :mod:`torchmetrics_forked_amd.models` (torchvision-identical
 unless ``backbone_weights`` is given).  The per-layer head — channel L2-normalisation of both feature maps,
 squared difference, 1×1 linear layer and spatial mean — runs as ONE fused gfx950 kernel per layer
 (``tmx::lpips_head``) when no autograd graph is needed; with gradients (or on CPU) the eager formulation is used.
+On that fused path the fp32 VGG16 trunk runs its thirteen 3×3 convolutions as ``tmx::conv3x3_relu`` (split-f16 matrix-core
+products, ``csrc/conv3x3.hip``); the other trunks and every other call keep ``nn.Conv2d``.
 With ``pretrained=True`` the linear heads are the published LPIPS v0.1 weights shipped with the package
 (``models/lpips_heads.safetensors``, the same values as the reference's ``lpips_models/{net}.pth``), or a LPIPS
 ``.pth`` given as ``model_path`` (loaded ``weights_only=True``).  The backbone trunks are random unless
@@ -18,6 +20,7 @@ from torch import Tensor, nn
 from typing_extensions import Literal
 
 from torchmetrics_forked_amd import ops
+from torchmetrics_forked_amd.ops import image as image_ops
 from torchmetrics_forked_amd.models.backbones import alexnet_features, squeezenet1_1_features, vgg16_features
 
 _SLICES = {
@@ -32,6 +35,15 @@ _FEATURES = {"alex": alexnet_features, "vgg": vgg16_features, "squeeze": squeeze
 # head reads the channels_last maps in place with four threads per pixel; BASELINE config 4: 0.329 vs 0.303 updates/s
 # (gpurun r7x; the first NHWC head, one thread per pixel, lost: 0.250, r7v / r7w)
 _CHANNELS_LAST = os.environ.get("TMX_LPIPS_CHANNELS_LAST", "1") != "0"
+# VGG16 trunk on the split-f16 matrix-core convolution (csrc/conv3x3.hip) instead of MIOpen's fp32 one;
+# TMX_LPIPS_TRUNK_NATIVE=0 keeps MIOpen.  Per-layer figures: profiles/lpips_trunk_bench.json (tools/lpips_trunk_bench.py)
+_TRUNK_NATIVE = os.environ.get("TMX_LPIPS_TRUNK_NATIVE", "1") != "0"
+
+
+def _native_layer(c_in: int, c_out: int) -> bool:
+    """Whether a 3x3 layer of the native trunk runs ``tmx::conv3x3_relu``; a layer class that measured slower than MIOpen
+    is sent back to ``nn.Conv2d`` here (none so far)."""
+    return (c_in == 3 or c_in % 32 == 0) and c_out % 64 == 0
 # LPIPS v0.1 linear heads (``tools/convert_lpips_heads.py`` from the reference's lpips_models/*.pth): the default for
 # ``pretrained=True``, as in the reference (``functional/image/lpips.py:318-325``)
 _HEADS_FILE = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "models", "lpips_heads.safetensors")
@@ -180,6 +192,50 @@ class _LPIPS(nn.Module):
                 conv = lin.model[-1]
                 conv.weight.copy_(heads[f"{net}.lin{i}"].reshape(conv.weight.shape))
 
+    def _native_trunk_ok(self, in0: Tensor, in1: Tensor, x0: Tensor, x1: Tensor, fused: bool) -> bool:
+        """The VGG16 trunk on ``tmx::conv3x3_relu``: the fused head's own condition (GPU, eval, no graph, not spatial), the
+        ``vgg`` backbone and two fp32 ``[B, 3, H, W]`` images (16-bit images are scaled into fp32 ``x0`` / ``x1`` and keep the
+        ``nn.Conv2d`` trunk, like everything else)."""
+        return (
+            fused
+            and _TRUNK_NATIVE
+            and self.pnet_type == "vgg"
+            and x0.dim() == 4
+            and in0.dtype == in1.dtype == torch.float32
+            and ops.native_inputs_ok(x0, x1, dtypes=(torch.float32,))
+        )
+
+    def _vgg_trunk_native(self, x: Tensor) -> List[Tensor]:
+        """The five tapped feature maps of ``self.net`` (channels_last fp32), its 3x3 convolutions with bias and ReLU run by
+        ``tmx::conv3x3_relu``; the max-pools stay ATen calls on the channels_last maps.  Each launch hands the per-image maximum
+        of its output to the next one (a max-pool cannot raise it), so only the network input is reduced on its own.  The packed
+        weight planes are cached per layer under the weight's ``(data_ptr, _version)``."""
+        cache = self.__dict__.setdefault("_trunk_planes", {})
+        outs, absmax, idx = [], None, 0
+        for s in self.net.slices:
+            layers = list(s)
+            i = 0
+            while i < len(layers):
+                layer = layers[i]
+                i += 1
+                idx += 1
+                if not isinstance(layer, nn.Conv2d):  # MaxPool2d
+                    x = layer(x)
+                    continue
+                relu = i < len(layers) and isinstance(layers[i], nn.ReLU)
+                i += relu
+                if not _native_layer(layer.in_channels, layer.out_channels):  # (see _native_layer: this class lost to MIOpen)
+                    x = layer(x)
+                    x, absmax = (x.relu_() if relu else x), None
+                    continue
+                key = (layer.weight.data_ptr(), layer.weight._version)
+                entry = cache.get(idx)
+                if entry is None or entry[0] != key:
+                    entry = cache[idx] = (key, *image_ops.pack_conv3x3_weights(layer.weight))
+                x, absmax = image_ops.conv3x3_relu(x, entry[1], entry[2], layer.bias, absmax, relu=relu)
+            outs.append(x)
+        return outs
+
     def forward(self, in0: Tensor, in1: Tensor, retperlayer: bool = False, normalize: bool = False) -> Union[Tensor, Tuple[Tensor, List[Tensor]]]:
         if normalize:
             in0, in1 = 2 * in0 - 1, 2 * in1 - 1
@@ -196,7 +252,10 @@ class _LPIPS(nn.Module):
                 self.__dict__["_trunk_cl"] = True
             x0 = x0.contiguous(memory_format=torch.channels_last)
             x1 = x1.contiguous(memory_format=torch.channels_last)
-        outs0, outs1 = self.net(x0), self.net(x1)
+        if self._native_trunk_ok(in0, in1, x0, x1, fused):
+            outs0, outs1 = self._vgg_trunk_native(x0), self._vgg_trunk_native(x1)
+        else:
+            outs0, outs1 = self.net(x0), self.net(x1)
         res = []
         for kk in range(self.L):
             if fused:

@@ -215,3 +215,26 @@ def gradient_tile() -> Tuple[int, int]:
     """``(fp32 columns per workgroup of the neighbour-difference kernels, rows per strip)``; 16-bit inputs take twice the columns."""
     columns, rows = torch.ops.tmx.gradient_tile()
     return int(columns), int(rows)
+
+
+def pack_conv3x3_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
+    """``tmx::conv3x3_pack`` (``csrc/conv3x3.hip``): splits an fp32 ``[C_out, C_in, 3, 3]`` weight (``C_in`` 3 or a multiple of 32, ``C_out`` a
+    multiple of 64) once into the f16 hi / lo planes ``tmx::conv3x3_relu`` streams, with one power-of-two shift per output channel;
+    returns ``(planes, shifts)``.  Raises for a weight that holds inf or NaN (one host read, paid once per weight version)."""
+    planes, shift, nonfinite = torch.ops.tmx.conv3x3_pack(weight.detach())
+    if int(nonfinite.item()):
+        raise ValueError("pack_conv3x3_weights: the weight holds inf or NaN")
+    return planes, shift
+
+
+def conv3x3_relu(
+    x: Tensor, w_planes: Tensor, w_shift: Tensor, bias: Tensor, x_absmax: Optional[Tensor] = None, relu: bool = True
+) -> Tuple[Tensor, Tensor]:
+    """``tmx::conv3x3_relu`` (``csrc/conv3x3.hip``): fp32 3x3 convolution, stride 1, zero padding 1, plus bias and optional ReLU, of ``x``
+    ``[B, C_in, H, W]`` with weights packed by :func:`pack_conv3x3_weights`, as split-f16 products on the matrix cores with fp32
+    accumulation.  ``x`` is read and the result ``y`` written in channels_last memory.  ``x_absmax`` ``[B]`` is max ``|x|`` of every image
+    (it sets that image's power-of-two scale; a value above the true maximum only costs low bits); ``None`` takes it by one
+    reduction launch.  Returns ``(y, y_absmax)``, so a chain of layers passes the second on.  No autograd."""
+    if x_absmax is None:
+        x_absmax = torch.ops.tmx.conv3x3_absmax(x)
+    return torch.ops.tmx.conv3x3_relu(x, w_planes, w_shift, bias, x_absmax, bool(relu))
