@@ -22,40 +22,13 @@
 //
 // Non-finite activations: an image whose max is inf / NaN is staged unscaled, so its own outputs go non-finite where the
 // composition's would; no other image reads its scale.  Weights are checked finite when packed.
-#include "common.h"
+#include "conv_split.h"
 
 #include <algorithm>
-#include <cfloat>
 
 namespace tmx {
 
 constexpr int kCvTH = 8, kCvTW = 16, kCvHaloW = kCvTW + 2, kCvHalo = (kCvTH + 2) * kCvHaloW;  // 180 halo pixels
-constexpr int kCvLd = 72;  // halves per LDS row: 32 hi | 32 lo | 8 pad (the 16 lanes of a ds_read_b128 group hit distinct bank quads)
-constexpr int kCvThreads = 256, kCvK = 32;
-typedef short cv_frag8 __attribute__((ext_vector_type(8)));
-typedef short cv_frag4 __attribute__((ext_vector_type(4)));
-typedef float cv_acc4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ cv_acc4 cv_mma(cv_frag8 a, cv_frag8 b, cv_acc4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(reinterpret_cast<__attribute__((ext_vector_type(8))) _Float16&>(a),
-                                                reinterpret_cast<__attribute__((ext_vector_type(8))) _Float16&>(b), c, 0, 0, 0);
-}
-
-// shift that puts a finite positive maximum in [2^14, 2^15); 0 for zero, inf and NaN
-__device__ __forceinline__ int cv_shift(float mx) {
-  int e = 0;
-  if (!(mx > 0.f && mx <= FLT_MAX)) return 0;
-  frexpf(mx, &e);
-  return 15 - e;
-}
-
-__device__ __forceinline__ void cv_split(float v, int s, short& hi, short& lo) {
-  const float t = ldexpf(v, s);
-  const __half h = __float2half_rn(t);
-  const __half l = __float2half_rn(t - __half2float(h));
-  hi = static_cast<short>(bits16<__half>(h));
-  lo = static_cast<short>(bits16<__half>(l));
-}
 
 // max |x| per image as a bit pattern (NaN orders above inf there, so a NaN anywhere makes the image's max NaN).
 // x: [B][n] fp32, out: [B] zero-initialised; chunks workgroups per image.

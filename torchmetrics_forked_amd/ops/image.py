@@ -238,3 +238,47 @@ def conv3x3_relu(
     if x_absmax is None:
         x_absmax = torch.ops.tmx.conv3x3_absmax(x)
     return torch.ops.tmx.conv3x3_relu(x, w_planes, w_shift, bias, x_absmax, bool(relu))
+
+
+def pack_conv_bn_weights(weight: Tensor, bn_weight: Tensor, bn_bias: Tensor, bn_mean: Tensor, bn_var: Tensor, eps: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """``tmx::conv_pack`` (``csrc/conv_taps.hip``): folds an eval-mode batch norm into an fp32 ``[C_out, C_in, KH, KW]`` weight (both channel
+    counts multiples of 16) in fp64, ``w' = w γ / sqrt(var + eps)`` and ``b' = β − mean γ / sqrt(var + eps)`` each rounded once to fp32, and
+    splits ``w'`` into the f16 hi / lo planes ``tmx::conv_bn_relu`` streams, one power-of-two shift per output channel; returns
+    ``(planes, shifts, b')``.  Raises if a folded value is inf or NaN (one host read, paid once per weight version)."""
+    planes, shift, bias, nonfinite = torch.ops.tmx.conv_pack(
+        weight.detach(), bn_weight.detach(), bn_bias.detach(), bn_mean.detach(), bn_var.detach(), float(eps)
+    )
+    if int(nonfinite.item()):
+        raise ValueError("pack_conv_bn_weights: the folded weight or bias holds inf or NaN")
+    return planes, shift, bias
+
+
+def conv_bn_relu(
+    x: Tensor,
+    w_planes: Tensor,
+    w_shift: Tensor,
+    bias: Tensor,
+    kernel_size: Tuple[int, int],
+    padding: Tuple[int, int] = (0, 0),
+    x_absmax: Optional[Tensor] = None,
+    out: Optional[Tensor] = None,
+    out_absmax: Optional[Tensor] = None,
+    c_off: int = 0,
+) -> Tuple[Tensor, Tensor]:
+    """``tmx::conv_bn_relu`` (``csrc/conv_taps.hip``): ``relu(bn(conv(x)))`` of a channels_last fp32 ``x`` ``[B, C_in, H, W]``, stride 1, taps
+    1x1, 3x3, 5x5, 1x7, 7x1, 1x3 or 3x1 with padding ``(0, 0)`` or same, weights packed by :func:`pack_conv_bn_weights`, as split-f16 products on
+    the matrix cores with fp32 accumulation.  The result goes into channels ``[c_off, c_off + C_out)`` of ``out``, a channels_last block that
+    may be wider (the branches of an Inception block share one), and its per-image maximum is folded into ``out_absmax`` ``[B]``; both are
+    allocated here when ``None``.  ``x_absmax`` ``[B]`` is max ``|x|`` per image (``None``: one reduction launch).  Returns
+    ``(out, out_absmax)``.  No autograd."""
+    kh, kw = kernel_size
+    x = x.contiguous(memory_format=torch.channels_last)
+    if x_absmax is None:
+        x_absmax = torch.ops.tmx.conv3x3_absmax(x)
+    if out is None:
+        shape = (x.shape[0], w_shift.numel(), x.shape[2] + 2 * padding[0] - kh + 1, x.shape[3] + 2 * padding[1] - kw + 1)
+        out = torch.empty(shape, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    if out_absmax is None:
+        out_absmax = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
+    torch.ops.tmx.conv_bn_relu(x, w_planes, w_shift, bias, x_absmax, out, out_absmax, int(c_off), kh, kw, int(padding[0]), int(padding[1]))
+    return out, out_absmax
